@@ -11,7 +11,13 @@ the NEIGHBOURING rank's first frame, recomputed locally as a 1-frame halo: weak 
 (torch.distributed / RCCL carries the timing barrier and the max-over-ranks only).
 
 `value` is the HBM-resident rate; consecutive steps read four DISTINCT input batches in turn (the sequence and its three mirror
-images: same statistics, 4 x 84 MB, more than the 256 MB Infinity Cache keeps).  The same line carries: `roofline` = the HBM
+images: same statistics, 4 x 84 MB, more than the 256 MB Infinity Cache keeps).
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what `value` needs: set-up, the untimed steps (W warm-up steps and as
+many more as a --full run takes before its timed region, without its events), the N timed steps, and the result line (`metric`,
+`value`, `unit`, `ms_per_step`, `higher_is_better`, `dtype`, the workload).  `--dump-outputs DIR` writes what the last timed step
+computed as DIR/*.npy (the inputs are the same from run to run for the same arguments).  Everything below is measured only with
+`--full`.  With it, the same line also carries: `roofline` = the HBM
 roofline of the dominant kernel (algorithmic bytes per launch / its live launch duration, HIP events on the library's stream inside
 the timed region, against 8 TB/s; `frac` = `frac_live`, with `frac_alone` = the same launch at pipeline depth 1 and both recomputed from
 the committed rocprofv3 files `roofline.rocprof_csv` names) with `roofline.per_kernel` for every kernel of the step; `step_spread` (the
@@ -48,6 +54,7 @@ CONFIGS = {
 HBM_PEAK_GBS = 8000.0            # MI355X HBM3E spec peak (MI355X_MICROARCH.md); the measured device-copy rate is reported beside it
 PROFILE_TAG = "r06_final"      # the round checkpoint under profiles/ that holds this build's rocprofv3 summaries (tools/round_checkpoint.sh)
 VALU_PEAK_GINSTR = 1228.8        # wave-instructions/s the chip can issue: 256 CUs x 4 SIMDs x 2.4 GHz / 2 cycles per wave64 op on a SIMD32
+DUMP_BUDGET_BYTES = 60 * 10 ** 6  # --dump-outputs: array bytes in all, under 64 MB with the files' headers (a seeded sample of the frames beyond it)
 
 
 def level_sizes(w, h, nlevels=NLEVELS, sf=SCALE):
@@ -524,13 +531,22 @@ class HbmWorkload:
         else:
             self.ex.profile(True, only=only)
 
-    def measure(self, steps, warmup, n_serial=3):
+    def measure(self, steps, warmup, n_serial=3, profile=True):
         """warm-up; the per-kernel durations at pipeline depth 1 (they name the dominant kernel); then the TIMED region: exactly `steps`
-        steps between barrier + device sync on both sides, only the dominant kernel's launches carrying events.  -> dict"""
+        steps between barrier + device sync on both sides, only the dominant kernel's launches carrying events.  profile=False (a plain
+        run): warm-up and the timed region alone, no events anywhere.  -> dict"""
         ctx = self.ctx
         for _ in range(warmup + self.DEPTH):
             self.step()
         self.sync_all()
+        if not profile:
+            # as many untimed steps as the per-kernel pass below takes (its steps + the refill of the lanes), without events: the timed
+            # region starts after the same number of steps as in a profiled run, and its last step reads the same input batch
+            for _ in range(n_serial + self.DEPTH):
+                self.step()
+            self.sync_all()
+            dt = timed_steps(self.step, self.sync_all, steps, ctx.dist, ctx.red_dev)
+            return {"dt": dt, "timed_variants": list(self.lane_variant)}
         serial = {}
         dom = "k_fast_score"
         if os.environ.get("UVO_BENCH_SKIP_SERIAL") != "1":   # (profile collection: a run that holds launches of ONE pipeline depth only)
@@ -571,6 +587,41 @@ class HbmWorkload:
         B, cap = self.B, self.cap
         return dict(n=o.n.cpu().numpy(), kp=o.kp.cpu().numpy().view(np.uint8).reshape(B + 1, cap, 28), de=o.desc.cpu().numpy(), i0=o.idx0.cpu().numpy(),
                     i1=o.idx1.cpu().numpy(), d0=o.d0.cpu().numpy().astype(np.uint16), d1=o.d1.cpu().numpy().astype(np.uint16))
+
+    def dump_last_step(self, out_dir, suffix="", budget=DUMP_BUDGET_BYTES):
+        """What the last step computed, as a caller of the path receives it, written as out_dir/<name><suffix>.npy in float32: per frame
+        the keypoint count, the valid keypoint rows (x, y, size, angle, response, octave, class_id) and descriptor bytes, and per pair
+        (frame p, frame p + 1) the knn-2 rows of frame p's keypoints.  Rows past a frame's count are not part of the result and are
+        left out.  If all frames exceed `budget` bytes, a fixed seeded sample of the frames is written; frame_index names them."""
+        B, cap = self.B, self.cap
+        o = self.outs[(self.counter[0] - 1) % self.DEPTH]
+        n = o.n.cpu().numpy().astype(np.int64)
+        kp = o.kp.cpu().numpy()
+        fields = np.concatenate([kp[..., :5], kp[..., 5:].view(np.int32).astype(np.float32)], axis=2)   # octave, class_id are int32 bits
+        de = o.desc.cpu().numpy()
+        knn = [a.cpu().numpy() for a in (o.idx0, o.d0, o.idx1, o.d1)]
+        per_frame = n * 4 * (7 + 32 + 4)   # keypoint fields + descriptor bytes + knn-2 rows, float32 each
+        frames = np.arange(B + 1)
+        if per_frame.sum() > budget:
+            take, used = [], 0
+            for f in np.random.default_rng(0).permutation(B + 1):
+                if used + per_frame[f] <= budget:
+                    take.append(f)
+                    used += per_frame[f]
+            frames = np.sort(np.array(take, dtype=np.int64))
+        pairs = frames[frames < B]
+        arrays = {
+            "frame_index": frames.astype(np.float32),
+            "n_keypoints": n[frames].astype(np.float32),
+            "keypoints": np.concatenate([fields[f, :n[f]] for f in frames]).reshape(-1, 7),
+            "descriptors": np.concatenate([de[f, :n[f]] for f in frames]).reshape(-1, 32).astype(np.float32),
+        }
+        for name, a in zip(("knn_idx0", "knn_dist0", "knn_idx1", "knn_dist1"), knn):
+            arrays[name] = np.concatenate([a[p, :n[p]] for p in pairs] + [np.zeros(0, a.dtype)]).astype(np.float32)
+        os.makedirs(out_dir, exist_ok=True)
+        for name, a in arrays.items():
+            np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
+        return {name: list(a.shape) for name, a in arrays.items()}
 
     def verify(self, host, timed_variants, pairs):
         """outputs of the timed buffers (both lanes' last results, already on the host) against the CPU oracle; a mismatch fails the run"""
@@ -764,6 +815,33 @@ def config3_record(ctx, steps, link):
     return rec
 
 
+def headline_record(args, cfg, B, steps, world, dt, depth, nring, k_mean):
+    """The fields of the result line that a plain run and a --full run share: the headline figure and what it was measured on."""
+    W, H, NFEAT = cfg["W"], cfg["H"], cfg["nfeat"]
+    return {
+        "metric": "frames/sec ORB extract+match, %dx%d @%d kp" % (W, H, NFEAT),
+        "value": round(B * steps * world / dt, 1),
+        "unit": "frames/s",
+        "n_gpus": world,
+        "steps": steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(dt / steps * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": "synthetic",
+        "config": {"workload": "%s: 1xMI355X per rank, batch=%d synthetic %dx%d mono frames (+1 halo frame: the neighbouring rank's first), %d feats, "
+                               "%d levels, fastTh %d, FullDetect extract + all-pairs 256-bit Hamming knn-2 of consecutive frames, HBM-resident I/O"
+                               % (cfg["name"], B, W, H, NFEAT, NLEVELS, FAST_TH),
+                   "generator": "SURVEY.md 8(d): value-noise texture + %d shapes + N(0,3) sensor noise per frame; camera motion = a small affine per "
+                                "frame inside 32-frame chains (u-vip-slam_amd/synth.py make_sequence, noise='sensor')" % cfg["n_shapes"],
+                   "batch_per_gpu": B, "sharding": "contiguous frame blocks of one global sequence, 1-frame halo from the neighbour, no collective",
+                   "pipeline_depth": depth, "mean_keypoints_per_frame": round(k_mean, 1),
+                   "input_batches_in_rotation": nring, "fast_mode": args.fast_mode},
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -771,11 +849,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", type=int, default=2, choices=sorted(CONFIGS))
     ap.add_argument("--batch", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-subrecords", action="store_true")
-    ap.add_argument("--no-verify", action="store_true")
-    ap.add_argument("--h2h", action="store_true", help="run the host-to-host sharder leg even with --no-subrecords")
-    ap.add_argument("--c3", action="store_true", help="run the configs[3] record even with --no-subrecords")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: per-kernel times and the rooflines, verification against the CPU oracle, the "
+                         "host-to-host leg, the sub-records and the CPU baseline (a plain run sets up, warms up, times the steps and prints the result)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; see HbmWorkload.dump_last_step)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no cpu_baseline")
+    ap.add_argument("--no-subrecords", action="store_true", help="with --full: no sub-records, no host-to-host leg")
+    ap.add_argument("--no-verify", action="store_true", help="with --full: no verification against the CPU oracle")
+    ap.add_argument("--h2h", action="store_true", help="with --full: run the host-to-host sharder leg even with --no-subrecords")
+    ap.add_argument("--c3", action="store_true", help="with --full: run the configs[3] record even with --no-subrecords")
     ap.add_argument("--matcher-stream", choices=["lane", "own"], default="lane",
                     help="where the matching of a batch is enqueued: in the extracting lane's stream (default) or in the matcher's own stream behind events")
     ap.add_argument("--fast-mode", choices=["adaptive", "two_pass", "single_pass"], default="adaptive",
@@ -784,7 +867,9 @@ def main():
     cfg = CONFIGS[args.config]
     W, H, NFEAT = cfg["W"], cfg["H"], cfg["nfeat"]
     B = args.batch or cfg["batch"]
-    steps = args.steps or cfg["steps"]
+    steps = args.steps if args.steps is not None else cfg["steps"]
+    if steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     rank = int(os.environ.get("RANK", "0"))
@@ -830,8 +915,19 @@ def main():
     d_imgs, d_ring, NRING = wl.d_ring[0], wl.d_ring, wl.NRING
     step, extract_only, sync_all = wl.step, wl.extract_only, wl.sync_all
 
-    m = wl.measure(steps, args.warmup)
-    dt, dom, serial, ktimes = m["dt"], m["dom"], m["serial"], m["ktimes"]
+    m = wl.measure(steps, args.warmup, profile=args.full)
+    dt = m["dt"]
+    if args.dump_outputs:
+        wl.dump_last_step(args.dump_outputs, "" if world == 1 else "_rank%d" % rank)
+    if not args.full:   # a plain run: the headline figure alone
+        if rank == 0:
+            n_kp = wl.outs[0].n.cpu().numpy()[:B]
+            print(json.dumps(headline_record(args, cfg, B, steps, world, dt, DEPTH, wl.NRING, float(n_kp.mean()))))
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+    dom, serial, ktimes = m["dom"], m["serial"], m["ktimes"]
     # ---- the timed buffers, on the host (both lanes' last results) ----
     host = [wl.download(o) for o in wl.outs]
     n_live = max(8, min(20, steps // 4))
@@ -1058,28 +1154,9 @@ def main():
                     "kernel_ms_per_step_unoverlapped": {k: round(v[0] / m["n_serial"], 4) for k, v in sorted(serial.items())},
                     "note": "bound says hbm because frac is the HBM fraction this record format asks for (algorithmic bytes per launch / live launch duration "
                             "/ 8 TB/s); the kernel itself is bound by instruction issue: issue_roofline"}
-        out = {
-            "metric": "frames/sec ORB extract+match, %dx%d @%d kp" % (W, H, NFEAT),
-            "value": round(value, 1),
-            "unit": "frames/s",
-            "n_gpus": world,
-            "steps": steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(dt / steps * 1e3, 4),
+        out = headline_record(args, cfg, B, steps, world, dt, DEPTH, NRING, k_mean)
+        out.update({
             "step_spread": step_spread(m, steps, DEPTH),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u8",
-            "data": "synthetic",
-            "config": {"workload": "%s: 1xMI355X per rank, batch=%d synthetic %dx%d mono frames (+1 halo frame: the neighbouring rank's first), %d feats, "
-                                   "%d levels, fastTh %d, FullDetect extract + all-pairs 256-bit Hamming knn-2 of consecutive frames, HBM-resident I/O"
-                                   % (cfg["name"], B, W, H, NFEAT, NLEVELS, FAST_TH),
-                       "generator": "SURVEY.md 8(d): value-noise texture + %d shapes + N(0,3) sensor noise per frame; camera motion = a small affine per "
-                                    "frame inside 32-frame chains (u-vip-slam_amd/synth.py make_sequence, noise='sensor')" % cfg["n_shapes"],
-                       "batch_per_gpu": B, "sharding": "contiguous frame blocks of one global sequence, 1-frame halo from the neighbour, no collective",
-                       "pipeline_depth": DEPTH, "mean_keypoints_per_frame": round(k_mean, 1),
-                       "input_batches_in_rotation": NRING, "fast_mode": args.fast_mode},
             "verified_frames": verified["frames"] if verified else 0,
             "verification": verified,
             "roofline": roofline,
@@ -1088,7 +1165,7 @@ def main():
             "issue_roofline": issue_roofline,
             "host_to_host": h2h,
             "sub_records": sub,
-        }
+        })
         if not args.no_cpu_baseline and world == 1:  # reported at N=1 only
             os.sched_setaffinity(0, all_cpus)
             out["cpu_baseline"] = cpu_baseline(frames[:B], cfg, c4_cpu)

@@ -17,7 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_two_ranks_gather_into_one_shared_region():
     env = dict(os.environ, UVO_BENCH_DRYRUN_ONE_GPU="1", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29583",
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch", "24", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-subrecords", "--h2h"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch", "24", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-subrecords", "--h2h"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, "bench.py --gpus 2 failed:\n%s\n%s" % (r.stdout[-3000:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -39,7 +39,7 @@ def test_two_ranks_run_the_configs3_record_with_its_host_gather():
     (here 2 ranks x 6 frames on device 0)."""
     env = dict(os.environ, UVO_BENCH_DRYRUN_ONE_GPU="1", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0", UVO_BENCH_C3_BATCH="6")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29585",
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch", "16", "--steps", "6", "--warmup", "1", "--no-cpu-baseline", "--no-subrecords", "--c3"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch", "16", "--steps", "6", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-subrecords", "--c3"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, "bench.py --gpus 2 --c3 failed:\n%s\n%s" % (r.stdout[-3000:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

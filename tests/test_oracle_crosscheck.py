@@ -1,10 +1,14 @@
 """Independent cross-checks of the oracle's [OCV-RECALL] primitives against third-party implementations that
-happen to be in the image: torch (bilinear interpolate, conv2d, reflect pad) and scikit-image 0.18.3 under /opt/conda/bin/python3.9
-(corner_fast, corner_orientations, its copy of the ORB sampling pattern), plus numpy's arctan2.
+happen to be in the image: torch (bilinear interpolate, conv2d, reflect pad) and scikit-image 0.18.3 (corner_fast, corner_orientations,
+its copy of the ORB sampling pattern, its descriptor loop), plus numpy's arctan2.  scikit-image is not importable by the suite's own
+interpreter: tests/crosscheck/skimage_probe.py ran under one that has it, and its outputs are stored in tests/golden/skimage_probe.npz,
+keyed by a digest of the exact inputs.  Re-record them (after a change to the inputs) with
+  UVO_SKIMAGE_PYTHON=<python with scikit-image 0.18.3> python -m pytest tests/test_oracle_crosscheck.py
 
 What this is NOT: a pin.  None of these is OpenCV; they agree with the oracle up to the tolerance each comparison states, which bounds
 the damage a wrong recollection could do -- a wrong half-pixel convention, tap table, border mode, ring order or patch shape fails
 here -- but the last grey level / tie is only settled by OpenCV 3.4.x itself (tools/pin/).  DESIGN.md section 5 says so."""
+import hashlib
 import os
 import subprocess
 import tempfile
@@ -13,7 +17,16 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PY39 = "/opt/conda/bin/python3.9"
+GOLDEN = os.path.join(ROOT, "tests", "golden", "skimage_probe.npz")
+RECORD_WITH = os.environ.get("UVO_SKIMAGE_PYTHON")   # set: run the probe live under this interpreter and rewrite GOLDEN
+_recorded = {}
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _record_golden():
+    yield
+    if RECORD_WITH and _recorded:
+        np.savez_compressed(GOLDEN, **{"%s.%s" % (key, name): v for key, out in _recorded.items() for name, v in out.items()})
 
 
 @pytest.fixture(scope="module")
@@ -99,15 +112,26 @@ def test_fast_atan2_is_within_its_documented_error_of_arctan2(oracle):
 
 
 def _skimage_probe(img, thresholds, corners, **extra):
-    if not os.path.exists(PY39):
-        pytest.skip("no /opt/conda/bin/python3.9 (scikit-image) in this image")
-    with tempfile.TemporaryDirectory() as td:
-        a, b = os.path.join(td, "in.npz"), os.path.join(td, "out.npz")
-        np.savez(a, img=img, thresholds=np.array(thresholds), corners=np.asarray(corners, np.int64), **extra)
-        r = subprocess.run([PY39, "-W", "ignore", os.path.join(ROOT, "tests", "crosscheck", "skimage_probe.py"), a, b], capture_output=True, text=True)
-        if r.returncode != 0:
-            pytest.skip("scikit-image probe failed: " + r.stderr[-300:])
-        return dict(np.load(b))
+    """scikit-image's answers for these inputs (tests/crosscheck/skimage_probe.py): the recorded ones, or live ones while re-recording."""
+    inputs = dict(img=img, thresholds=np.array(thresholds, np.int64), corners=np.asarray(corners, np.int64), **extra)
+    h = hashlib.sha256()
+    for name in sorted(inputs):
+        a = np.ascontiguousarray(inputs[name])
+        h.update(("%s %s %r;" % (name, a.dtype.str, a.shape)).encode())
+        h.update(a.tobytes())
+    key = h.hexdigest()[:16]
+    if RECORD_WITH:
+        with tempfile.TemporaryDirectory() as td:
+            a, b = os.path.join(td, "in.npz"), os.path.join(td, "out.npz")
+            np.savez(a, **inputs)
+            r = subprocess.run([RECORD_WITH, "-W", "ignore", os.path.join(ROOT, "tests", "crosscheck", "skimage_probe.py"), a, b], capture_output=True, text=True)
+            assert r.returncode == 0, "scikit-image probe failed: " + r.stderr[-300:]
+            _recorded[key] = dict(np.load(b))
+        return _recorded[key]
+    with np.load(GOLDEN) as g:
+        out = {n[len(key) + 1:]: g[n] for n in g.files if n.startswith(key + ".")}
+    assert out, "no recorded scikit-image output for these probe inputs (digest %s): they changed -- re-record %s (module docstring)" % (key, GOLDEN)
+    return out
 
 
 def test_fast_corner_set_equals_scikit_image(oracle, frames):

@@ -10,7 +10,7 @@ done
 done
 for v in octold octnew; do
   cp variants/libuvo_$v.so u-vip-slam_amd/libuvo.so
-  for i in 1 2; do python bench.py --no-cpu-baseline --no-subrecords --no-verify | python -c "
+  for i in 1 2; do python bench.py --full --no-cpu-baseline --no-subrecords --no-verify | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
 print('$v', d['value'], r['kernel_ms_per_step_unoverlapped'])" | tee -a $O/latency_oct_ab.txt; done

@@ -10,11 +10,11 @@ R=$GRAFT_REPO_ROOT
 cd $R
 O=gpurun_out/$TAG
 mkdir -p $O
-SHORT="--config $CFG --steps 2 --warmup 1 --no-cpu-baseline --no-subrecords --no-verify"
+SHORT="--full --config $CFG --steps 2 --warmup 1 --no-cpu-baseline --no-subrecords --no-verify"
 export UVO_BENCH_SKIP_SERIAL=1   # no depth-1 pass inside a depth-2 run: every launch of a file ran at the file's depth
 for D in 1 2; do
   export UVO_PIPELINE_DEPTH=$D
-  rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/kt$D -o kt -- python3 bench.py --config $CFG --no-cpu-baseline --no-subrecords --no-verify > $O/bench_under_rocprof_depth$D.json 2> $O/kt$D.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/kt$D -o kt -- python3 bench.py --full --config $CFG --no-cpu-baseline --no-subrecords --no-verify > $O/bench_under_rocprof_depth$D.json 2> $O/kt$D.err
   find $O/kt$D -name "*kernel_stats.csv" -exec cp {} $O/kernel_stats_depth$D.csv \;
 done
 unset UVO_BENCH_SKIP_SERIAL

@@ -14,7 +14,7 @@ else
   for f in variants/libuvo_*.so; do
     cp $f u-vip-slam_amd/libuvo.so
     echo -n "$(basename $f .so | sed s/libuvo_//): "
-    python bench.py --no-cpu-baseline --no-subrecords --no-verify "$@" 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['roofline']['kernel_ms_per_step_unoverlapped'])"
+    python bench.py --full --no-cpu-baseline --no-subrecords --no-verify "$@" 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['roofline']['kernel_ms_per_step_unoverlapped'])"
   done
   cp /tmp/libuvo_plain.so u-vip-slam_amd/libuvo.so
 fi
