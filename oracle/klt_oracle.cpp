@@ -9,6 +9,7 @@
 // tracker are summed in raster order over the window here (the scalar path); a SIMD OpenCV build sums four partial lanes, so
 // positions agree with any real build only to float rounding -- the GPU parity tests use a tolerance for the same reason.
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstring>
 
@@ -93,7 +94,13 @@ void KltPyramid::build(const uint8_t* img, int w, int h, ptrdiff_t stride, int w
   }
 }
 
-static inline int cv_floor(float v) { return (int)floorf(v); }
+// cvFloor as OpenCV computes it on x86 (_mm_cvtss_si32 of the value rounded down): NaN and values outside the int range give
+// INT_MIN, cvtss2si's "integer indefinite".  Stated explicitly: a float -> int cast of such a value is undefined behaviour.  INT_MIN
+// fails the image-bounds tests, so a NaN or out-of-range coordinate rejects its point.
+static inline int cv_floor(float v) {
+  if (!(v >= -2147483648.f && v < 2147483648.f)) return INT_MIN;
+  return (int)floorf(v);
+}
 static inline int cv_round(float v) { return (int)lrintf(v); }
 #define KLT_DESCALE(x, n) (((x) + (1 << ((n)-1))) >> (n))
 

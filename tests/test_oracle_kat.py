@@ -563,6 +563,35 @@ def test_klt_pyramid_and_tracker_known_answers(oracle, synth):
     _, st, er = oracle.klt_track(p0, p1, np.array([[-40.0, 50.0], [100.0, 100.0]], np.float32))
     assert st[0] == 0 and er[0] == 0 and st[1] == 1
 
+
+def test_klt_non_finite_coordinates_are_rejected(oracle, synth):
+    """cvFloor on x86 (cvtss2si) gives INT_MIN for NaN and for values outside the int range, so such a coordinate fails the image-bounds
+    test: in prev_pts the point is rejected at every level (status 0, err 0); in the initial flow the template is still built, so err
+    is the level-0 minimum eigenvalue and the first iteration rejects the point (status 0)."""
+    base = synth.make_frame(21, 400, 320)
+    shifted = np.roll(np.roll(base, 3, axis=1), -2, axis=0)
+    p0, p1 = oracle.klt_pyramid(base), oracle.klt_pyramid(shifted)
+    nan, inf = np.float32(np.nan), np.float32(np.inf)
+    good = [200.0, 150.0]
+    bad = [[nan, 150.0], [200.0, nan], [inf, 150.0], [-inf, 150.0], [200.0, inf], [200.0, -inf], [3e38, 150.0], [-3e38, 150.0],
+           [2.0 ** 31, 150.0], [-(2.0 ** 31), 150.0]]
+    pts = np.array(bad + [good], np.float32)
+    _, st, er = oracle.klt_track(p0, p1, pts)
+    assert st[-1] == 1 and er[-1] > 1e-4
+    assert (st[:-1] == 0).all() and (er[:-1] == 0).all(), (st, er)
+    _, ref_st, ref_err = oracle.klt_track(p0, p1, np.array([good], np.float32))
+    assert ref_st[0] == 1 and ref_err[0] > 0
+    for init in ([nan, 150.0], [200.0, nan], [nan, nan]):
+        for ml in (0, 3, 5):
+            nxt, st, er = oracle.klt_track(p0, p1, np.array([good], np.float32), np.array([init], np.float32), max_level=ml)
+            _, st_ok, er_ok = oracle.klt_track(p0, p1, np.array([good], np.float32), max_level=ml)
+            assert st[0] == 0 and st_ok[0] == 1 and er[0] == er_ok[0] > 0, (init, ml, st, er, er_ok)
+            assert np.isnan(nxt[0]).any()
+    # without iterations the initial flow is never read: the point keeps status 1
+    _, st, er = oracle.klt_track(p0, p1, np.array([good], np.float32), np.array([[nan, nan]], np.float32), max_count=0)
+    assert st[0] == 1 and er[0] == ref_err[0]
+
+
 def test_strip_plan_tiles_every_window_exactly_once():
     """Host check of the wavefront strip plan shared by k_fast_score and k_gauss7 (csrc/strip_plan.hpp, compiled with a plain C++
     compiler): every pixel of a window belongs to exactly one (item, sub-strip); the plan never needs more wavefront-rows than
@@ -609,7 +638,8 @@ def test_klt_association_order_only_moves_decisions_at_their_thresholds(oracle, 
     0.01 px are points whose termination tests ran within 10 % of their thresholds (an iteration more or less)."""
     rng = np.random.default_rng(81)
     total = far = 0
-    for (w, h), win, ml in (((640, 512), (21, 21), 5), ((752, 480), (15, 15), 3)):
+    # 9/3 and 25/7: the EuRoC settings of the reference (Data/euroc.yaml, Data/EuroC/V1_3.yaml); 25 x 25 sums run over 625 terms
+    for (w, h), win, ml in (((640, 512), (21, 21), 5), ((752, 480), (15, 15), 3), ((752, 480), (9, 9), 3), ((752, 480), (25, 25), 7)):
         a = synth.make_frame(6000 + w, w, h)
         b = synth.warp_frame(a, 6001 + w)
         pa, pb = oracle.klt_pyramid(a, win, ml), oracle.klt_pyramid(b, win, ml)

@@ -1209,16 +1209,19 @@ class KLT:
             raise UvoError(rc, "uvo_klt_read_level")
         return img, der
 
-    def track(self, prev_slot, next_slot, prev_pts, next_pts0=None, max_count=30, epsilon=0.01, min_eig_threshold=1e-4):
-        """Returns (next_pts, status, err)."""
+    def track(self, prev_slot, next_slot, prev_pts, next_pts0=None, max_count=30, epsilon=0.01, min_eig_threshold=1e-4, max_level=None):
+        """Returns (next_pts, status, err).  max_level: the top pyramid level tracked (None: the handle's; clamped to the levels built)."""
         p0 = np.ascontiguousarray(prev_pts, np.float32).reshape(-1, 2)
         p1 = p0.copy() if next_pts0 is None else np.ascontiguousarray(next_pts0, np.float32).reshape(-1, 2).copy()
         st, er = np.zeros(len(p0), np.uint8), np.zeros(len(p0), np.float32)
-        rc = lib.uvo_klt_track(self._h, prev_slot, next_slot, _ptr(p0), _ptr(p1), len(p0), self.max_level, int(max_count), float(epsilon),
+        rc = lib.uvo_klt_track(self._h, prev_slot, next_slot, _ptr(p0), _ptr(p1), len(p0), self._level(max_level), int(max_count), float(epsilon),
                                float(min_eig_threshold), _ptr(st), _ptr(er))
         if rc:
             raise UvoError(rc, "uvo_klt_track")
         return p1, st, er
+
+    def _level(self, max_level):
+        return self.max_level if max_level is None else int(max_level)
 
     def undistort(self, cam, pts):
         """Tracking::undistort_point (src/Tracking.cc:1265-1283) for an (n, 2) float32 array; cam: CameraModel."""
@@ -1229,15 +1232,15 @@ class KLT:
             raise UvoError(rc, "uvo_undistort_points")
         return out
 
-    def track_undistorted(self, prev_slot, next_slot, prev_pts, cam, next_pts0=None, max_count=30, epsilon=0.01, min_eig_threshold=1e-4):
-        """uvo_klt_track_undistorted: the LK step + undistort_point of both point sets in one call.
+    def track_undistorted(self, prev_slot, next_slot, prev_pts, cam, next_pts0=None, max_count=30, epsilon=0.01, min_eig_threshold=1e-4, max_level=None):
+        """uvo_klt_track_undistorted: the LK step + undistort_point of both point sets in one call; max_level as in track().
         Returns (next, status, err, prev_un, next_un)."""
         a = np.ascontiguousarray(prev_pts, np.float32).reshape(-1, 2)
         b = a.copy() if next_pts0 is None else np.ascontiguousarray(next_pts0, np.float32).reshape(-1, 2).copy()
         n = len(a)
         st, er = np.zeros(n, np.uint8), np.zeros(n, np.float32)
         pu, nu = np.zeros((n, 2), np.float32), np.zeros((n, 2), np.float32)
-        rc = lib.uvo_klt_track_undistorted(self._h, prev_slot, next_slot, _ptr(a), _ptr(b), n, self.max_level, int(max_count), float(epsilon), float(min_eig_threshold),
+        rc = lib.uvo_klt_track_undistorted(self._h, prev_slot, next_slot, _ptr(a), _ptr(b), n, self._level(max_level), int(max_count), float(epsilon), float(min_eig_threshold),
                                            ctypes.byref(cam), _ptr(st), _ptr(er), _ptr(pu), _ptr(nu))
         if rc:
             raise UvoError(rc, "uvo_klt_track_undistorted")

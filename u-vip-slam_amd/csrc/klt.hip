@@ -13,6 +13,7 @@
 //       differently from a raster-order CPU loop, so positions agree with the CPU statement to float rounding (tolerance in
 //       the parity test), as they do between OpenCV's own scalar and SIMD builds.
 #include <algorithm>
+#include <climits>
 #include <cstring>
 #include <vector>
 
@@ -94,6 +95,11 @@ __device__ __forceinline__ float wave_sum_f(float v) {
 
 #define KLT_DESCALE(x, n) (((x) + (1 << ((n)-1))) >> (n))
 
+// cvFloor as OpenCV's x86 build computes it (cvtss2si of the value rounded down): NaN and values outside the int range give INT_MIN,
+// which fails the image-bounds tests.  A bare (int)floorf() becomes v_cvt_i32_f32, which turns NaN into 0: a NaN coordinate would
+// pass the bounds test and be tracked on NaN weights.
+__device__ __forceinline__ int klt_floor(float v) { return (v >= -2147483648.f && v < 2147483648.f) ? (int)floorf(v) : INT_MIN; }
+
 // NP = window pixels per lane (win_w * win_h <= 64 * NP)
 template <int NP>
 __global__ __launch_bounds__(256) void k_klt_track(KltGeom G, const uint8_t* __restrict__ img0, const int16_t* __restrict__ der0,
@@ -129,7 +135,7 @@ __global__ __launch_bounds__(256) void k_klt_track(KltGeom G, const uint8_t* __r
     }
     nx = nextx, ny = nexty;
     prevx -= halfx, prevy -= halfy;
-    const int ipx = (int)floorf(prevx), ipy = (int)floorf(prevy);
+    const int ipx = klt_floor(prevx), ipy = klt_floor(prevy);
     if (ipx < -win_w || ipx >= L.w || ipy < -win_h || ipy >= L.h) {
       if (level == 0) ok = false, e_out = 0.f;
       continue;
@@ -171,7 +177,7 @@ __global__ __launch_bounds__(256) void k_klt_track(KltGeom G, const uint8_t* __r
     float pdx = 0.f, pdy = 0.f;
     const uint8_t* Jlvl = img1 + L.ioff;
     for (int j = 0; j < max_count; ++j) {
-      const int inx = (int)floorf(nextx), iny = (int)floorf(nexty);
+      const int inx = klt_floor(nextx), iny = klt_floor(nexty);
       if (inx < -win_w || inx >= L.w || iny < -win_h || iny >= L.h) {
         if (level == 0) ok = false;
         break;
