@@ -1091,6 +1091,117 @@ def test_frustum_then_search_by_projection_chain(uvo, oracle, synth):
     m.close()
 
 
+def _reuse_scene(uvo, rng, n, M):
+    """Random key points on a 752x480 frame, map points near them (back-projected for the frustum call), three Fuse targets and three
+    triangulation pairs: inputs for every matcher entry point at one size."""
+    W, H = 752, 480
+    fx, fy, cx, cy = 458.654, 457.296, 367.215, 248.375
+    sf = (np.float32(1.2) ** np.arange(8)).astype(np.float32)
+
+    def frame(k):
+        kp = np.zeros(k, uvo.KEYPOINT_DTYPE)
+        kp["x"], kp["y"] = rng.uniform(0, W, k), rng.uniform(0, H, k)
+        kp["octave"], kp["angle"] = rng.integers(0, 8, k), rng.uniform(0, 360, k)
+        return kp, rng.integers(0, 256, (k, 32), dtype=np.uint8)
+
+    kp, de = frame(n)
+    src = rng.integers(0, n, M)
+    R, t, Ow = _random_pose(rng)
+    z = rng.uniform(2, 12, M)
+    pc = np.stack([(kp["x"][src] - cx) / fx * z, (kp["y"][src] - cy) / fy * z, z], 1) + rng.normal(0, 0.01, (M, 3))
+    xyz = ((pc - t) @ R.astype(np.float64)).astype(np.float32)
+    nrm = xyz - Ow
+    nrm = (nrm / np.linalg.norm(nrm, axis=1, keepdims=True)).astype(np.float32)
+    mxd = (np.linalg.norm(xyz - Ow, axis=1) * sf[kp["octave"][src]] * rng.uniform(0.95, 1.05, M)).astype(np.float32)
+    mnd = (mxd / sf[7]).astype(np.float32)
+    targets = []
+    for _ in range(3):
+        tkp, tde = frame(n)
+        Rt, tt, Owt = _random_pose(rng)
+        targets.append((tkp, tde, uvo.CameraPose.make(Rt, tt, Owt, fx, fy, cx, cy, (0.0, 0.0, float(W), float(H))), sf))
+    pairs = []
+    for _ in range(3):
+        kp2, de2 = frame(n)
+        F12 = (np.array([[0, 0, 0], [0, 0, -1], [0, 1, 0]], np.float32) + rng.normal(0, 3e-4, (3, 3)).astype(np.float32))
+        pairs.append((uvo.FeatureVector(_bow_groups(rng, de2, 40)), kp2, de2, (rng.random(n) < 0.3).astype(np.uint8), F12, (sf * sf * np.float32(400)).astype(np.float32)))
+    return dict(
+        kp=kp, de=de, sf=sf, bounds=(0, 0, W, H), cam=uvo.CameraPose.make(R, t, Ow, fx, fy, cx, cy, (0.0, 0.0, float(W), float(H))),
+        q=rng.integers(0, 256, (n, 32), dtype=np.uint8), t=rng.integers(0, 256, (n, 32), dtype=np.uint8),
+        mask=(rng.random((n, n)) < 0.3).astype(np.uint8),
+        lists=[_noisy_copies(rng, de, rng.integers(0, n, int(c)), 0.1, 1.0) for c in rng.integers(0, 40, M // 4)],
+        mp_desc=_noisy_copies(rng, de, src, 0.06, 0.6), xyz=xyz, nrm=nrm, mnd=mnd, mxd=mxd,
+        u=(kp["x"][src] + rng.normal(0, 2, M)).astype(np.float32), v=(kp["y"][src] + rng.normal(0, 2, M)).astype(np.float32),
+        level=np.clip(kp["octave"][src] + rng.integers(-1, 2, M), 0, 7).astype(np.int32), valid=(rng.random(M) < 0.9).astype(np.uint8),
+        vc=np.where(rng.random(M) < 0.5, 0.999, 0.9).astype(np.float32), kf_angle=rng.uniform(0, 360, M).astype(np.float32),
+        usable=(rng.random(M) < 0.9).astype(np.uint8), taken=np.where(rng.random(n) < 0.05, 7777, -1).astype(np.int32),
+        fv1=uvo.FeatureVector(_bow_groups(rng, de, 40)), has1=(rng.random(n) < 0.25).astype(np.uint8), targets=targets, pairs=pairs)
+
+
+def _reuse_calls(S, th):
+    """(name, call(matcher) -> outputs) for the entry points whose device staging grows with the input"""
+    def sbp(m):
+        a = S["taken"].copy()
+        nm = m.SearchByProjection(S["kp"], S["de"], S["bounds"], a, S["u"], S["v"], S["level"], S["vc"], S["valid"], S["mp_desc"], S["sf"], th)
+        return a, nm
+
+    def frustum(m):
+        a = S["taken"].copy()
+        out = m.SearchPointsInFrustum(S["kp"], S["de"], a, S["cam"], S["xyz"], S["nrm"], S["mnd"], S["mxd"], S["usable"], S["mp_desc"], S["sf"],
+                                      1.2, 0.5, th, want_projections=True)
+        return (a,) + tuple(out)
+
+    def windows(m):
+        a = S["taken"].copy()
+        nm = m.SearchByProjectionKF(S["kp"], S["de"], S["bounds"], a, S["u"], S["v"], S["level"], S["valid"], S["mp_desc"], S["kf_angle"], S["sf"],
+                                    th, 100)
+        return (a, nm) + tuple(m.FuseSearch(S["kp"], S["de"], S["bounds"], S["u"], S["v"], S["level"], S["valid"], S["mp_desc"], S["sf"], th))
+
+    def triangulation(m):
+        m.SearchForTriangulationBatch(S["fv1"], S["kp"], S["de"], S["has1"], S["pairs"])
+        return sum((m.SearchForTriangulationNext(k, S["has1"]) for k in range(len(S["pairs"]))), ())
+
+    return [("knn2 with a mask", lambda m: m.knn2(S["q"], S["t"], S["mask"])),
+            ("distance matrix", lambda m: (m.distance_matrix(S["q"], S["t"]),)),
+            ("distinctive descriptors", lambda m: m.distinctive_descriptors(S["lists"])),
+            ("points in frustum", frustum),   # before the other searches: its candidate lists start from the 8-per-point request
+            ("SearchByProjection", sbp),
+            ("window searches", windows),
+            ("FuseBatch", lambda m: m.FuseBatch(S["targets"], S["xyz"], S["nrm"], S["mnd"], S["mxd"], S["usable"], S["mp_desc"], th)),
+            ("SearchForTriangulationBatch", triangulation)]
+
+
+def test_one_matcher_through_small_large_small_inputs(uvo):
+    """A long-lived handle against fresh ones.  The large step outgrows every buffer the handle grows on demand: the mask (300 x 300 ->
+    4000 x 4000), the distance matrix, the medoid staging (~2000 rows -> ~39000), the frustum block and its candidate lists (th = 15 on
+    8000 map points truncates the 8-per-point first run, so the match stage is repeated), and the window-search / batch slots (8000
+    queries, 4000 targets).  Every call must give, bit for bit, what the same call on a fresh handle gives; the second small step must
+    also give what the first one gave."""
+    cfg = dict(max_query=4096, max_train=4096, max_map_points=8192)
+    m = uvo.ORBmatcher(0.8, True, **cfg)
+    first = None
+    for step, (seed, n, M, th) in enumerate(((5, 300, 400, 3.0), (6, 4000, 8000, 15.0), (5, 300, 400, 3.0))):
+        S = _reuse_scene(uvo, np.random.default_rng(seed), n, M)
+        got = []
+        for name, call in _reuse_calls(S, th):
+            out = [np.asarray(x) for x in call(m)]
+            fresh = uvo.ORBmatcher(0.8, True, **cfg)
+            ref = [np.asarray(x) for x in call(fresh)]
+            fresh.close()
+            for k, (g, r) in enumerate(zip(out, ref)):
+                assert g.dtype == r.dtype and g.shape == r.shape and g.tobytes() == r.tobytes(), "step %d, %s, output %d" % (step, name, k)
+            got.append(out)
+        if step == 0:
+            first = got
+            assert got[4][1] > 20 and (got[5][2] >= 0).sum() > 20, "the small step must find matches"
+        elif step == 1:
+            assert got[3][1] > 1000 and got[4][1] > 1000, "the large step must find matches"
+        else:
+            for name_out, a, b in zip(_reuse_calls(S, th), first, got):
+                for k, (x, y) in enumerate(zip(a, b)):
+                    assert x.tobytes() == y.tobytes(), "%s output %d differs between the two small steps" % (name_out[0], k)
+    m.close()
+
+
 def _random_vocabulary(rng, k=10, L=4, weighting=0, normalize=1):
     """A k-ary tree of depth <= L whose node descriptors are noisy copies of their parent's (so the descent is meaningful);
     ~5 % of the inner candidates stop early as leaves, ~5 % of the words are stop words (weight 0)."""

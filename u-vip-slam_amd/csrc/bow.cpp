@@ -7,10 +7,6 @@
 
 #include "common.hpp"
 
-namespace uvo {
-void launch_bow_descend(hipStream_t s, const int32_t* d_child_start, const int32_t* d_children, const uint8_t* d_desc, const int32_t* d_word_id,
-                        const double* d_weight, int L, const uint8_t* d_feat, int n, int levelsup, int32_t* d_word, double* d_w, int32_t* d_node);
-}
 using namespace uvo;
 
 struct uvo_vocabulary {

@@ -644,10 +644,6 @@ void launch_haloc(hipStream_t s, const float* d_proj, int num_proj, int proj_str
   hipLaunchKernelGGL(k_haloc, dim3((num_proj * 32 + 63) / 64), dim3(64), 0, s, d_proj, num_proj, proj_stride, d_desc, n, d_hash);
 }
 
-// grid build shared with search.hip
-void launch_grid_build(hipStream_t s, const uvo_keypoint* d_kp, const uint8_t* d_desc, int n, int min_x, int min_y, int max_x, int max_y,
-                       int32_t* d_cell_start, int32_t* d_cell_items, int32_t* d_cell_of_kp);
-
 void launch_win_count(hipStream_t s, const uvo_keypoint* d_kp, const uint8_t* d_desc, int n, int min_x, int min_y, int max_x, int max_y, int nq,
                       const float* d_qx, const float* d_qy, const float* d_qr, const int32_t* d_qmin, const int32_t* d_qmax,
                       const uint8_t* d_qvalid, const uint8_t* d_qdesc, int32_t* d_cell_start, int32_t* d_cell_items, int32_t* d_cell_of_kp,

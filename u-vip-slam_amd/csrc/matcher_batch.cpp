@@ -20,17 +20,6 @@
 #include "matcher_priv.hpp"
 
 namespace uvo {
-void launch_group_dist_pairs(hipStream_t s, int nq, int total, const int32_t* d_cand_start, const int32_t* d_cand_idx, const uint8_t* d_qdesc,
-                             const uint8_t* d_tdesc, const int32_t* d_tlevel, const int32_t* d_q_pair, const int32_t* d_pair_base, const float* d_f12,
-                             const float* d_qx, const float* d_qy, const float* d_tx, const float* d_ty, const float* d_sigma2, int sig_stride,
-                             uint32_t* d_cand);
-void launch_fuse_walk(hipStream_t s, const uvo_keypoint* d_kp, const uint8_t* d_desc, int n, int min_x, int min_y, int max_x, int max_y, int nmp,
-                      const uint8_t* d_valid, const float* d_u, const float* d_v, const int32_t* d_level, const uint8_t* d_mp_desc, const float* d_sf, float th,
-                      int32_t* d_cell_start, int32_t* d_cell_items, int32_t* d_cell_of_kp, int32_t* d_best_idx, int32_t* d_best_dist);
-void launch_project(hipStream_t s, int mode, const uvo_camera_pose& cam, int n, const float* d_xyz, const float* d_normal, const float* d_min,
-                    const float* d_max, const float* d_max_raw, const uint8_t* d_usable, const float* d_sf, int nlevels, float log_sf, float cos_limit,
-                    uint8_t* d_valid, float* d_u, float* d_v, int32_t* d_level, float* d_cos);
-
 // what uvo_search_for_triangulation_batch leaves in the handle for the _next calls
 struct TriBatch {
   int n1 = 0, n_pairs = 0;
@@ -50,53 +39,6 @@ void tri_batch_free(void* p) { delete static_cast<TriBatch*>(p); }
 using namespace uvo;
 
 namespace {
-enum BatchSlot { B0 = 24, B_QDESC = B0, B_TDESC, B_TLEVEL, B_START, B_CIDX, B_QPAIR, B_MISC, B_CAND };  // scratch slots of the batched forms
-
-int ensure(uvo_matcher* m, int slot, size_t bytes, void** out) {
-  DevBuf& b = m->scratch[slot];
-  if (bytes > b.cap) {
-    if (b.p) {
-      if (hipStreamSynchronize(m->stream) != hipSuccess) return matcher_fail(UVO_E_HIP, "hipStreamSynchronize failed");
-      (void)hipFree(b.p);
-      b.p = nullptr, b.cap = 0;
-    }
-    const size_t want = bytes + bytes / 2 + 256;
-    uint8_t* p = nullptr;
-    int rc = m_alloc(&p, want);
-    if (rc) return rc;
-    b.p = p, b.cap = want;
-  }
-  *out = b.p;
-  return UVO_OK;
-}
-template <class T>
-int upload(uvo_matcher* m, int slot, const T* src, size_t count, T** dev) {
-  void* p = nullptr;
-  int rc = ensure(m, slot, std::max<size_t>(count, 1) * sizeof(T), &p);
-  if (rc) return rc;
-  *dev = static_cast<T*>(p);
-  if (count && src && hipMemcpyAsync(p, src, count * sizeof(T), hipMemcpyHostToDevice, m->stream) != hipSuccess) return matcher_fail(UVO_E_HIP, "hipMemcpyAsync failed");
-  return UVO_OK;
-}
-#define RC(call)                   \
-  do {                             \
-    const int _rc = (call);        \
-    if (_rc != UVO_OK) return _rc; \
-  } while (0)
-
-int check_fv(const uvo_feature_vector* fv, int n) {
-  if (!fv || fv->n_nodes < 0) return matcher_fail(UVO_E_BADARG, "null feature vector");
-  if (fv->n_nodes == 0) return UVO_OK;
-  if (!fv->node || !fv->start || !fv->feat) return matcher_fail(UVO_E_BADARG, "null feature vector arrays");
-  for (int k = 0; k < fv->n_nodes; ++k) {
-    if (k && fv->node[k] <= fv->node[k - 1]) return matcher_fail(UVO_E_BADARG, "feature vector node ids must be strictly ascending");
-    if (fv->start[k + 1] < fv->start[k]) return matcher_fail(UVO_E_BADARG, "feature vector offsets must be non-decreasing");
-  }
-  for (int e = fv->start[0]; e < fv->start[fv->n_nodes]; ++e)
-    if (fv->feat[e] < 0 || fv->feat[e] >= n) return matcher_fail(UVO_E_BADARG, "feature index outside the keypoint range");
-  return UVO_OK;
-}
-
 // ORBmatcher::ComputeThreeMaxima (src/ORBmatcher.cc:1748-1789) on bin populations
 void three_maxima(const int* hist, int L, int& ind1, int& ind2, int& ind3) {
   int max1 = 0, max2 = 0, max3 = 0;
@@ -125,12 +67,12 @@ extern "C" {
 
 int uvo_search_for_triangulation_batch(uvo_matcher* m, const uvo_feature_vector* fv1, const uvo_keypoint* kp1, int n1, const uint8_t* desc1,
                                        const uint8_t* has_mp1, int n_pairs, const uvo_triangulation_pair* pairs) {
-  if (!m) return matcher_fail(UVO_E_BADARG, "null handle");
+  if (!m) return fail(UVO_E_BADARG, "null handle");
   tri_batch_free(m->tri_batch);
   m->tri_batch = nullptr;
-  if (n1 < 0 || n_pairs < 0 || n_pairs > 4096) return matcher_fail(UVO_E_BADARG, "bad sizes");
-  if (n_pairs > 0 && !pairs) return matcher_fail(UVO_E_BADARG, "null pointer");
-  if (n1 > 0 && (!kp1 || !desc1 || !has_mp1)) return matcher_fail(UVO_E_BADARG, "null pointer");
+  if (n1 < 0 || n_pairs < 0 || n_pairs > 4096) return fail(UVO_E_BADARG, "bad sizes");
+  if (n_pairs > 0 && !pairs) return fail(UVO_E_BADARG, "null pointer");
+  if (n1 > 0 && (!kp1 || !desc1 || !has_mp1)) return fail(UVO_E_BADARG, "null pointer");
   RC(check_fv(fv1, n1));
   TriBatch* tb = new TriBatch();
   struct Guard {
@@ -151,11 +93,11 @@ int uvo_search_for_triangulation_batch(uvo_matcher* m, const uvo_feature_vector*
   size_t nt = 0;
   for (int p = 0; p < n_pairs; ++p) {
     const uvo_triangulation_pair& P = pairs[p];
-    if (P.n2 < 0 || P.n2 > 65535 || P.nlevels < 1 || P.nlevels > 64) return matcher_fail(UVO_E_BADARG, "bad pair (at most 65535 keypoints, 1 <= nlevels <= 64)");
-    if (P.n2 > 0 && (!P.kp2 || !P.desc2 || !P.has_mp2 || !P.sigma2)) return matcher_fail(UVO_E_BADARG, "null pointer in a pair");
+    if (P.n2 < 0 || P.n2 > 65535 || P.nlevels < 1 || P.nlevels > 64) return fail(UVO_E_BADARG, "bad pair (at most 65535 keypoints, 1 <= nlevels <= 64)");
+    if (P.n2 > 0 && (!P.kp2 || !P.desc2 || !P.has_mp2 || !P.sigma2)) return fail(UVO_E_BADARG, "null pointer in a pair");
     RC(check_fv(P.fv2, P.n2));
     for (int k = 0; k < P.n2; ++k)
-      if (P.kp2[k].octave < 0 || P.kp2[k].octave >= P.nlevels) return matcher_fail(UVO_E_BADARG, "keypoint level outside the pair's sigma table");
+      if (P.kp2[k].octave < 0 || P.kp2[k].octave >= P.nlevels) return fail(UVO_E_BADARG, "keypoint level outside the pair's sigma table");
     TriBatch::Pair& Q = tb->pairs[p];
     Q.n2 = P.n2, Q.q_begin = (int)tb->q_idx1.size();
     Q.angle2.resize(P.n2);
@@ -226,14 +168,14 @@ int uvo_search_for_triangulation_batch(uvo_matcher* m, const uvo_feature_vector*
     int32_t *d_tlevel, *d_start, *d_cidx, *d_il;
     float* d_fl;
     uint32_t* d_cand;
-    RC(upload(m, B_QDESC, qdesc.data(), qdesc.size(), &d_qdesc));
-    RC(upload(m, B_TDESC, tdesc.data(), tdesc.size(), &d_tdesc));
-    RC(upload(m, B_TLEVEL, tlevel.data(), tlevel.size(), &d_tlevel));
-    RC(upload(m, B_START, tb->start.data(), tb->start.size(), &d_start));
-    RC(upload(m, B_CIDX, cidx.data(), cidx.size(), &d_cidx));
-    RC(upload(m, B_QPAIR, il.data(), il.size(), &d_il));
-    RC(upload(m, B_MISC, fl.data(), fl.size(), &d_fl));
-    RC(upload<uint32_t>(m, B_CAND, nullptr, (size_t)total, &d_cand));
+    RC(upload(m, S_QDESC, qdesc.data(), qdesc.size(), &d_qdesc));
+    RC(upload(m, S_TDESC, tdesc.data(), tdesc.size(), &d_tdesc));
+    RC(upload(m, S_TLEVEL, tlevel.data(), tlevel.size(), &d_tlevel));
+    RC(upload(m, S_START, tb->start.data(), tb->start.size(), &d_start));
+    RC(upload(m, S_CIDX, cidx.data(), cidx.size(), &d_cidx));
+    RC(upload(m, S_QPAIR, il.data(), il.size(), &d_il));
+    RC(upload(m, S_MISC, fl.data(), fl.size(), &d_fl));
+    RC(reserve(m, S_CAND, (size_t)total, &d_cand));
     const float *d_qx = d_fl, *d_qy = d_qx + nq, *d_tx = d_qy + nq, *d_ty = d_tx + nt, *d_f12 = d_ty + nt, *d_sigma = d_f12 + f12.size();
     launch_group_dist_pairs(m->stream, nq, total, d_start, d_cidx, d_qdesc, d_tdesc, d_tlevel, d_il, d_il + nq, d_f12, d_qx, d_qy, d_tx, d_ty, d_sigma, sig_stride,
                             d_cand);
@@ -248,17 +190,17 @@ int uvo_search_for_triangulation_batch(uvo_matcher* m, const uvo_feature_vector*
 }
 
 int uvo_search_for_triangulation_next(uvo_matcher* m, int pair, const uint8_t* has_mp1_now, int check_orientation, int32_t* match12, int* n_matches) {
-  if (!m || !n_matches) return matcher_fail(UVO_E_BADARG, "null pointer");
+  if (!m || !n_matches) return fail(UVO_E_BADARG, "null pointer");
   *n_matches = 0;
   const TriBatch* tb = static_cast<const TriBatch*>(m->tri_batch);
-  if (!tb) return matcher_fail(UVO_E_BADARG, "no batch: call uvo_search_for_triangulation_batch first");
-  if (pair < 0 || pair >= tb->n_pairs) return matcher_fail(UVO_E_BADARG, "pair outside the batch");
+  if (!tb) return fail(UVO_E_BADARG, "no batch: call uvo_search_for_triangulation_batch first");
+  if (pair < 0 || pair >= tb->n_pairs) return fail(UVO_E_BADARG, "pair outside the batch");
   if (tb->n1 == 0) return UVO_OK;
-  if (!match12 || !has_mp1_now) return matcher_fail(UVO_E_BADARG, "null pointer");
+  if (!match12 || !has_mp1_now) return fail(UVO_E_BADARG, "null pointer");
   for (int i = 0; i < tb->n1; ++i) {
     match12[i] = -1;
     // the batch only prepared the features that had no map point when it began; one that LOST its point since would be a query now
-    if (tb->has_mp1[i] && !has_mp1_now[i]) return matcher_fail(UVO_E_BADARG, "a feature lost its map point since the batch began: start a new batch");
+    if (tb->has_mp1[i] && !has_mp1_now[i]) return fail(UVO_E_BADARG, "a feature lost its map point since the batch began: start a new batch");
   }
   const TriBatch::Pair& P = tb->pairs[pair];
   std::vector<uint8_t> vbMatched2(P.n2, 0);
@@ -323,14 +265,14 @@ int uvo_search_for_triangulation_next(uvo_matcher* m, int pair, const uint8_t* h
 int uvo_fuse_batch(uvo_matcher* m, int n_targets, const uvo_fuse_target* targets, int nmp, const float* xyz, const float* normal,
                    const float* min_distance_inv, const float* max_distance_inv, const uint8_t* usable, const uint8_t* mp_desc, float th,
                    int32_t* best_idx, int32_t* best_dist) {
-  if (!m) return matcher_fail(UVO_E_BADARG, "null handle");
-  if (n_targets < 0 || nmp < 0) return matcher_fail(UVO_E_BADARG, "bad sizes");
+  if (!m) return fail(UVO_E_BADARG, "null handle");
+  if (n_targets < 0 || nmp < 0) return fail(UVO_E_BADARG, "bad sizes");
   if (n_targets == 0 || nmp == 0) return UVO_OK;
-  if (!targets || !xyz || !normal || !min_distance_inv || !max_distance_inv || !mp_desc || !best_idx || !best_dist) return matcher_fail(UVO_E_BADARG, "null pointer");
+  if (!targets || !xyz || !normal || !min_distance_inv || !max_distance_inv || !mp_desc || !best_idx || !best_dist) return fail(UVO_E_BADARG, "null pointer");
   for (int t = 0; t < n_targets; ++t) {
     const uvo_fuse_target& T = targets[t];
-    if (T.n < 0 || T.n > 65535 || T.nlevels < 1 || T.nlevels > 64 || T.max_x <= T.min_x || T.max_y <= T.min_y) return matcher_fail(UVO_E_BADARG, "bad target");
-    if (!T.scale_factors || (T.n > 0 && (!T.kp || !T.desc))) return matcher_fail(UVO_E_BADARG, "null pointer in a target");
+    if (T.n < 0 || T.n > 65535 || T.nlevels < 1 || T.nlevels > 64 || T.max_x <= T.min_x || T.max_y <= T.min_y) return fail(UVO_E_BADARG, "bad target");
+    if (!T.scale_factors || (T.n > 0 && (!T.kp || !T.desc))) return fail(UVO_E_BADARG, "null pointer in a target");
   }
   UVO_HIP_CHECK(hipSetDevice(m->device));
   hipStream_t s = m->stream;
@@ -349,29 +291,31 @@ int uvo_fuse_batch(uvo_matcher* m, int n_targets, const uvo_fuse_target* targets
   memcpy(&fl[(size_t)nmp * 7], max_distance_inv, (size_t)nmp * sizeof(float));
   float* d_fl;
   uint8_t *d_usable = nullptr, *d_mpdesc;
-  RC(upload(m, B_MISC, fl.data(), fl.size(), &d_fl));
-  if (usable) RC(upload(m, B_QPAIR, usable, (size_t)nmp, &d_usable));
-  RC(upload(m, B_QDESC, mp_desc, (size_t)nmp * 32, &d_mpdesc));
+  RC(upload(m, S_MISC, fl.data(), fl.size(), &d_fl));
+  if (usable) RC(upload(m, S_QVALID, usable, (size_t)nmp, &d_usable));
+  RC(upload(m, S_MPDESC, mp_desc, (size_t)nmp * 32, &d_mpdesc));
   // per-point projection outputs (reused by every target) and the results of all targets
-  uint8_t* d_work;
-  RC(upload<uint8_t>(m, B_CIDX, nullptr, (size_t)nmp * 16, &d_work));
-  float* d_u = reinterpret_cast<float*>(d_work);
-  float* d_v = d_u + nmp;
-  int32_t* d_level = reinterpret_cast<int32_t*>(d_v + nmp);
-  uint8_t* d_valid = reinterpret_cast<uint8_t*>(d_level + nmp);
-  int32_t* d_best;
-  RC(upload<int32_t>(m, B_CAND, nullptr, (size_t)2 * n_targets * nmp, &d_best));
+  float *d_u, *d_v;
+  int32_t *d_level, *d_best;
+  uint8_t* d_valid;
+  RC(reserve(m, S_PX, (size_t)nmp, &d_u));
+  RC(reserve(m, S_PY, (size_t)nmp, &d_v));
+  RC(reserve(m, S_LEVEL, (size_t)nmp, &d_level));
+  RC(reserve(m, S_INVIEW, (size_t)nmp, &d_valid));
+  RC(reserve(m, S_MATCH, (size_t)2 * n_targets * nmp, &d_best));
   int max_n = 1, max_lev = 1;
   for (int t = 0; t < n_targets; ++t) max_n = std::max(max_n, targets[t].n), max_lev = std::max(max_lev, targets[t].nlevels);
   // every buffer a target needs is sized for the largest one up front: nothing grows (and synchronises) inside the loop
   uvo_keypoint* d_kp;
   uint8_t* d_desc;
   float* d_sf;
-  int32_t* d_cells;
-  RC(upload<uvo_keypoint>(m, B_TLEVEL, nullptr, (size_t)max_n, &d_kp));
-  RC(upload<uint8_t>(m, B_TDESC, nullptr, (size_t)max_n * 32, &d_desc));
-  RC(upload<int32_t>(m, B_START, nullptr, (size_t)64 * 48 + 1 + 2 * (size_t)max_n + 64, &d_cells));
-  d_sf = reinterpret_cast<float*>(d_cells + 64 * 48 + 1 + 2 * (size_t)max_n);
+  int32_t *d_cell_start, *d_cell_items, *d_cell_of;
+  RC(reserve(m, S_KP, (size_t)max_n, &d_kp));
+  RC(reserve(m, S_TDESC, (size_t)max_n * 32, &d_desc));
+  RC(reserve(m, S_SCALE, (size_t)max_lev, &d_sf));
+  RC(reserve(m, S_CELL_START, (size_t)kGridCells + 1, &d_cell_start));
+  RC(reserve(m, S_CELL_ITEMS, (size_t)max_n, &d_cell_items));
+  RC(reserve(m, S_CELL_OF, (size_t)max_n, &d_cell_of));
   for (int t = 0; t < n_targets; ++t) {
     const uvo_fuse_target& T = targets[t];
     int32_t* bi = d_best + (size_t)t * nmp;
@@ -387,8 +331,8 @@ int uvo_fuse_batch(uvo_matcher* m, int n_targets, const uvo_fuse_target* targets
     // projection tests of Fuse (:1037-1075) with this target's pose, then the window walk on its grid
     launch_project(s, UVO_PROJECT_FUSE, T.cam, nmp, d_fl, d_fl + (size_t)nmp * 3, d_fl + (size_t)nmp * 6, d_fl + (size_t)nmp * 7, nullptr, d_usable, d_sf,
                    T.nlevels, 0.f, 0.f, d_valid, d_u, d_v, d_level, nullptr);
-    launch_fuse_walk(s, d_kp, d_desc, T.n, T.min_x, T.min_y, T.max_x, T.max_y, nmp, d_valid, d_u, d_v, d_level, d_mpdesc, d_sf, th, d_cells,
-                     d_cells + 64 * 48 + 1, d_cells + 64 * 48 + 1 + max_n, bi, bd);
+    launch_fuse_walk(s, d_kp, d_desc, T.n, T.min_x, T.min_y, T.max_x, T.max_y, nmp, d_valid, d_u, d_v, d_level, d_mpdesc, d_sf, th, d_cell_start,
+                     d_cell_items, d_cell_of, bi, bd);
   }
   UVO_HIP_CHECK(hipGetLastError());
   UVO_HIP_CHECK(hipMemcpyAsync(best_idx, d_best, (size_t)n_targets * nmp * 4, hipMemcpyDeviceToHost, s));

@@ -9,97 +9,14 @@
 #include "matcher_priv.hpp"
 #include "uvo_math.hpp"
 
-namespace uvo {
-void launch_win_count(hipStream_t s, const uvo_keypoint* d_kp, const uint8_t* d_desc, int n, int min_x, int min_y, int max_x, int max_y, int nq,
-                      const float* d_qx, const float* d_qy, const float* d_qr, const int32_t* d_qmin, const int32_t* d_qmax,
-                      const uint8_t* d_qvalid, const uint8_t* d_qdesc, int32_t* d_cell_start, int32_t* d_cell_items, int32_t* d_cell_of_kp,
-                      int32_t* d_cand_cnt, int32_t* d_cand_start);
-void launch_win_fill(hipStream_t s, const uvo_keypoint* d_kp, const uint8_t* d_desc, int n, int min_x, int min_y, int max_x, int max_y, int nq,
-                     const float* d_qx, const float* d_qy, const float* d_qr, const int32_t* d_qmin, const int32_t* d_qmax,
-                     const uint8_t* d_qvalid, const uint8_t* d_qdesc, const int32_t* d_cell_start, const int32_t* d_cell_items,
-                     const int32_t* d_cand_start, uint32_t* d_cand);
-void launch_group_dist(hipStream_t s, int nq, int total, const int32_t* d_cand_start, const int32_t* d_cand_idx, const uint8_t* d_qdesc,
-                       const uint8_t* d_tdesc, const int32_t* d_tlevel, const float* f12, const float* d_qx, const float* d_qy,
-                       const float* d_tx, const float* d_ty, const float* d_sigma2, uint32_t* d_cand);
-void launch_match_resolve(hipStream_t s, int nq, int nt, const int32_t* d_cand_start, const uint32_t* d_cand, const uint8_t* d_blocked, int rule,
-                          int max_dist, float nn_ratio, int exclusive, int32_t* d_owner, int32_t* d_owner_next, int32_t* d_match,
-                          int32_t* d_mdist, int32_t* d_n_matches);
-void launch_match_resolve_steal(hipStream_t s, int nq, int nt, const int32_t* d_cand_start, const uint32_t* d_cand, int max_dist, float nn_ratio,
-                                int32_t* d_head, int32_t* d_nxt, int32_t* d_tmp, int32_t* d_match, int32_t* d_mdist);
-void launch_steal_finalize(hipStream_t s, int nq, const int32_t* d_holder, int32_t* d_match, int32_t* d_mdist, int32_t* d_n_matches);
-void launch_rot_filter(hipStream_t s, int nq, const float* d_qangle, const float* d_tangle, int32_t* d_match, int32_t* d_mdist,
-                       int32_t* d_n_matches);
-void launch_project_sim3(hipStream_t s, const float* r_own, const float* t_own, const float* s_r, const float* t, const uvo_camera_pose& cam, int n,
-                         const float* d_xyz, const float* d_min, const float* d_max, const uint8_t* d_usable, const float* d_sf, int nlevels,
-                         uint8_t* d_valid, float* d_u, float* d_v, int32_t* d_level);
-void launch_project(hipStream_t s, int mode, const uvo_camera_pose& cam, int n, const float* d_xyz, const float* d_normal, const float* d_min,
-                    const float* d_max, const float* d_max_raw, const uint8_t* d_usable, const float* d_sf, int nlevels, float log_sf, float cos_limit, uint8_t* d_valid,
-                    float* d_u, float* d_v, int32_t* d_level, float* d_cos);
-void launch_haloc(hipStream_t s, const float* d_proj, int num_proj, int proj_stride, const uint8_t* d_desc, int n, float* d_hash);
-}  // namespace uvo
-
 using namespace uvo;
 
 namespace {
 
-enum Slot {  // uvo_matcher::scratch
-  S_KP = 0, S_TDESC, S_BLOCKED, S_QX, S_QY, S_QR, S_QMIN, S_QMAX, S_QVALID, S_QDESC, S_QANGLE, S_TANGLE, S_TLEVEL, S_CELL_START, S_CELL_ITEMS,
-  S_CELL_OF, S_CNT, S_START, S_CAND, S_CIDX, S_OWNER, S_OWNER2, S_MATCH, S_MISC
-};
-
-// device buffer of at least `bytes` in slot `slot` (contents undefined after growth); nullptr + error code on failure
-int ensure(uvo_matcher* m, int slot, size_t bytes, void** out) {
-  DevBuf& b = m->scratch[slot];
-  if (bytes > b.cap) {
-    if (b.p) {
-      hipError_t e = hipStreamSynchronize(m->stream);
-      if (e != hipSuccess) {
-        hip_err_set(e, "hipStreamSynchronize");
-        return UVO_E_HIP;
-      }
-      hipFree(b.p);
-      b.p = nullptr, b.cap = 0;
-    }
-    const size_t want = bytes + bytes / 2 + 256;
-    uint8_t* p = nullptr;
-    int rc = m_alloc(&p, want);
-    if (rc) return rc;
-    b.p = p, b.cap = want;
-  }
-  *out = b.p;
-  return UVO_OK;
-}
-
-template <class T>
-int upload(uvo_matcher* m, int slot, const T* src, size_t count, T** dev) {
-  void* p = nullptr;
-  int rc = ensure(m, slot, std::max<size_t>(count, 1) * sizeof(T), &p);
-  if (rc) return rc;
-  *dev = static_cast<T*>(p);
-  if (count && src) {
-    hipError_t e = hipMemcpyAsync(p, src, count * sizeof(T), hipMemcpyHostToDevice, m->stream);
-    if (e != hipSuccess) {
-      hip_err_set(e, "hipMemcpyAsync");
-      return UVO_E_HIP;
-    }
-  }
-  return UVO_OK;
-}
-template <class T>
-int reserve(uvo_matcher* m, int slot, size_t count, T** dev) {
-  return upload<T>(m, slot, nullptr, count, dev);
-}
-
-#define RC(call)                   \
-  do {                             \
-    const int _rc = (call);        \
-    if (_rc != UVO_OK) return _rc; \
-  } while (0)
-
 int check_rule(const uvo_match_rule* r) {
-  if (!r) return matcher_fail(UVO_E_BADARG, "null rule");
-  if (r->rule < UVO_RULE_BEST_RATIO_SAME_LEVEL || r->rule > UVO_RULE_INIT_STEAL) return matcher_fail(UVO_E_BADARG, "unknown rule");
-  if (r->max_dist < 0 || r->max_dist > 256) return matcher_fail(UVO_E_BADARG, "max_dist outside 0..256");
+  if (!r) return fail(UVO_E_BADARG, "null rule");
+  if (r->rule < UVO_RULE_BEST_RATIO_SAME_LEVEL || r->rule > UVO_RULE_INIT_STEAL) return fail(UVO_E_BADARG, "unknown rule");
+  if (r->max_dist < 0 || r->max_dist > 256) return fail(UVO_E_BADARG, "max_dist outside 0..256");
   return UVO_OK;
 }
 
@@ -107,20 +24,21 @@ int check_rule(const uvo_match_rule* r) {
 int finish(uvo_matcher* m, int nq, int nt, const int32_t* d_start, const uint32_t* d_cand, const uint8_t* d_blocked, const uvo_match_rule* rule,
            const float* d_qangle, const float* d_tangle, int32_t* match, int32_t* dist, int* n_matches) {
   hipStream_t s = m->stream;
-  int32_t *d_owner, *d_owner2, *d_match;
+  int32_t *d_owner, *d_match;
   RC(reserve(m, S_OWNER, (size_t)nt, &d_owner));
-  RC(reserve(m, S_OWNER2, (size_t)nt, &d_owner2));
   RC(reserve(m, S_MATCH, (size_t)2 * nq + 1, &d_match));
   int32_t* d_mdist = d_match + nq;
   int32_t* d_nm = d_match + 2 * nq;
   if (rule->rule == UVO_RULE_INIT_STEAL) {
     // accepts (displaced ones included) -> rotation filter over all of them -> only the queries still holding their target survive
     int32_t* d_tmp;
-    RC(reserve(m, S_OWNER2, (size_t)3 * nq + 1, &d_tmp));  // accept list links [nq] + the sweep's scratch [2 nq]
+    RC(reserve(m, S_STEAL, (size_t)3 * nq + 1, &d_tmp));  // accept list links [nq] + the sweep's scratch [2 nq]
     launch_match_resolve_steal(s, nq, nt, d_start, d_cand, rule->max_dist, rule->nn_ratio, d_owner, d_tmp, d_tmp + nq, d_match, d_mdist);
     if (rule->check_orientation) launch_rot_filter(s, nq, d_qangle, d_tangle, d_match, d_mdist, d_nm);
     launch_steal_finalize(s, nq, d_owner, d_match, d_mdist, d_nm);
   } else {
+    int32_t* d_owner2;
+    RC(reserve(m, S_OWNER2, (size_t)nt, &d_owner2));
     launch_match_resolve(s, nq, nt, d_start, d_cand, d_blocked, rule->rule, rule->max_dist, rule->nn_ratio, rule->exclusive ? 1 : 0, d_owner, d_owner2,
                          d_match, d_mdist, d_nm);
     if (rule->check_orientation) launch_rot_filter(s, nq, d_qangle, d_tangle, d_match, d_mdist, d_nm);
@@ -152,19 +70,6 @@ void for_shared_nodes(const uvo_feature_vector* a, const uvo_feature_vector* b, 
   }
 }
 
-int check_fv(const uvo_feature_vector* fv, int n) {
-  if (!fv || fv->n_nodes < 0) return matcher_fail(UVO_E_BADARG, "null feature vector");
-  if (fv->n_nodes == 0) return UVO_OK;
-  if (!fv->node || !fv->start || !fv->feat) return matcher_fail(UVO_E_BADARG, "null feature vector arrays");
-  for (int k = 0; k < fv->n_nodes; ++k) {
-    if (k && fv->node[k] <= fv->node[k - 1]) return matcher_fail(UVO_E_BADARG, "feature vector node ids must be strictly ascending");
-    if (fv->start[k + 1] < fv->start[k]) return matcher_fail(UVO_E_BADARG, "feature vector offsets must be non-decreasing");
-  }
-  for (int e = fv->start[0]; e < fv->start[fv->n_nodes]; ++e)
-    if (fv->feat[e] < 0 || fv->feat[e] >= n) return matcher_fail(UVO_E_BADARG, "feature index outside the keypoint range");
-  return UVO_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -173,21 +78,21 @@ int uvo_match_windows(uvo_matcher* m, const uvo_keypoint* kp, int n, const uint8
                       int max_x, int max_y, int nq, const float* qx, const float* qy, const float* qr, const int32_t* qmin_level,
                       const int32_t* qmax_level, const uint8_t* qvalid, const uint8_t* qdesc, const float* qangle, const uvo_match_rule* rule,
                       int32_t* match, int32_t* dist, int* n_matches) {
-  if (!m) return matcher_fail(UVO_E_BADARG, "null handle");
+  if (!m) return fail(UVO_E_BADARG, "null handle");
   if (n_matches) *n_matches = 0;
   RC(check_rule(rule));
-  if (rule->rule == UVO_RULE_TRIANGULATION) return matcher_fail(UVO_E_BADARG, "the triangulation rule needs caller-given candidates");
-  if (n < 0 || nq < 0 || n > 65535 || max_x <= min_x || max_y <= min_y) return matcher_fail(UVO_E_BADARG, "bad sizes (at most 65535 keypoints)");
+  if (rule->rule == UVO_RULE_TRIANGULATION) return fail(UVO_E_BADARG, "the triangulation rule needs caller-given candidates");
+  if (n < 0 || nq < 0 || n > 65535 || max_x <= min_x || max_y <= min_y) return fail(UVO_E_BADARG, "bad sizes (at most 65535 keypoints)");
   if (nq == 0) return UVO_OK;
-  if (!match || !qx || !qy || !qr || !qmin_level || !qmax_level || !qvalid || !qdesc) return matcher_fail(UVO_E_BADARG, "null pointer");
-  if (rule->check_orientation && !qangle) return matcher_fail(UVO_E_BADARG, "check_orientation needs query angles");
+  if (!match || !qx || !qy || !qr || !qmin_level || !qmax_level || !qvalid || !qdesc) return fail(UVO_E_BADARG, "null pointer");
+  if (rule->check_orientation && !qangle) return fail(UVO_E_BADARG, "check_orientation needs query angles");
   if (n == 0) {
     for (int i = 0; i < nq; ++i) match[i] = -1;
     if (dist)
       for (int i = 0; i < nq; ++i) dist[i] = -1;
     return UVO_OK;
   }
-  if (!kp || !desc) return matcher_fail(UVO_E_BADARG, "null pointer");
+  if (!kp || !desc) return fail(UVO_E_BADARG, "null pointer");
   UVO_HIP_CHECK(hipSetDevice(m->device));
   hipStream_t s = m->stream;
   uvo_keypoint* d_kp;
@@ -211,7 +116,7 @@ int uvo_match_windows(uvo_matcher* m, const uvo_keypoint* kp, int n, const uint8
     RC(upload(m, S_QANGLE, qangle, (size_t)nq, &d_qangle));
     RC(upload(m, S_TANGLE, tangle.data(), (size_t)n, &d_tangle));
   }
-  RC(reserve(m, S_CELL_START, (size_t)64 * 48 + 1, &d_cell_start));
+  RC(reserve(m, S_CELL_START, (size_t)kGridCells + 1, &d_cell_start));
   RC(reserve(m, S_CELL_ITEMS, (size_t)n, &d_cell_items));
   RC(reserve(m, S_CELL_OF, (size_t)n, &d_cell_of));
   RC(reserve(m, S_CNT, (size_t)nq + 1, &d_cnt));
@@ -232,26 +137,26 @@ int uvo_match_windows(uvo_matcher* m, const uvo_keypoint* kp, int n, const uint8
 int uvo_match_groups(uvo_matcher* m, int nq, const uint8_t* qdesc, const float* qangle, int nt, const uint8_t* tdesc, const float* tangle,
                      const int32_t* tlevel, const uint8_t* tblocked, const int32_t* cand_start, const int32_t* cand_idx,
                      const uvo_epipolar* epi, const uvo_match_rule* rule, int32_t* match, int32_t* dist, int* n_matches) {
-  if (!m) return matcher_fail(UVO_E_BADARG, "null handle");
+  if (!m) return fail(UVO_E_BADARG, "null handle");
   if (n_matches) *n_matches = 0;
   RC(check_rule(rule));
-  if (nq < 0 || nt < 0 || nt > 65535) return matcher_fail(UVO_E_BADARG, "bad sizes (at most 65535 targets)");
+  if (nq < 0 || nt < 0 || nt > 65535) return fail(UVO_E_BADARG, "bad sizes (at most 65535 targets)");
   if (nq == 0) return UVO_OK;
-  if (!match || !cand_start || !qdesc) return matcher_fail(UVO_E_BADARG, "null pointer");
-  if (cand_start[0] != 0) return matcher_fail(UVO_E_BADARG, "cand_start[0] must be 0");
+  if (!match || !cand_start || !qdesc) return fail(UVO_E_BADARG, "null pointer");
+  if (cand_start[0] != 0) return fail(UVO_E_BADARG, "cand_start[0] must be 0");
   for (int i = 0; i < nq; ++i)
-    if (cand_start[i + 1] < cand_start[i]) return matcher_fail(UVO_E_BADARG, "cand_start must be non-decreasing");
+    if (cand_start[i + 1] < cand_start[i]) return fail(UVO_E_BADARG, "cand_start must be non-decreasing");
   const int total = cand_start[nq];
-  if (total > 0 && (!cand_idx || !tdesc)) return matcher_fail(UVO_E_BADARG, "null pointer");
+  if (total > 0 && (!cand_idx || !tdesc)) return fail(UVO_E_BADARG, "null pointer");
   for (int e = 0; e < total; ++e)
-    if (cand_idx[e] < 0 || cand_idx[e] >= nt) return matcher_fail(UVO_E_BADARG, "candidate index outside the target range");
-  if (rule->check_orientation && (!qangle || !tangle)) return matcher_fail(UVO_E_BADARG, "check_orientation needs query and target angles");
-  if (rule->rule == UVO_RULE_BEST_RATIO_SAME_LEVEL && !tlevel) return matcher_fail(UVO_E_BADARG, "this rule needs target levels");
+    if (cand_idx[e] < 0 || cand_idx[e] >= nt) return fail(UVO_E_BADARG, "candidate index outside the target range");
+  if (rule->check_orientation && (!qangle || !tangle)) return fail(UVO_E_BADARG, "check_orientation needs query and target angles");
+  if (rule->rule == UVO_RULE_BEST_RATIO_SAME_LEVEL && !tlevel) return fail(UVO_E_BADARG, "this rule needs target levels");
   if (rule->rule == UVO_RULE_TRIANGULATION && epi) {
     if (!epi->q_x || !epi->q_y || !epi->t_x || !epi->t_y || !epi->sigma2 || !tlevel || epi->nlevels < 1)
-      return matcher_fail(UVO_E_BADARG, "incomplete epipolar description");
+      return fail(UVO_E_BADARG, "incomplete epipolar description");
     for (int t = 0; t < nt; ++t)
-      if (tlevel[t] < 0 || tlevel[t] >= epi->nlevels) return matcher_fail(UVO_E_BADARG, "target level outside the sigma table");
+      if (tlevel[t] < 0 || tlevel[t] >= epi->nlevels) return fail(UVO_E_BADARG, "target level outside the sigma table");
   }
   UVO_HIP_CHECK(hipSetDevice(m->device));
   hipStream_t s = m->stream;
@@ -286,17 +191,17 @@ int uvo_search_by_projection_kf(uvo_matcher* m, const uvo_keypoint* kp, int n, c
                                 int32_t* assigned, int nmp, const float* u, const float* v, const int32_t* level, const uint8_t* valid,
                                 const uint8_t* mp_desc, const float* kf_angle, const float* scale_factors, int nlevels, float th, int orb_dist,
                                 int check_orientation, int* n_matches) {
-  if (!m || !n_matches) return matcher_fail(UVO_E_BADARG, "null pointer");
+  if (!m || !n_matches) return fail(UVO_E_BADARG, "null pointer");
   *n_matches = 0;
-  if (n < 0 || nmp < 0 || nlevels < 1) return matcher_fail(UVO_E_BADARG, "bad sizes");
+  if (n < 0 || nmp < 0 || nlevels < 1) return fail(UVO_E_BADARG, "bad sizes");
   if (n == 0 || nmp == 0) return UVO_OK;
-  if (!assigned || !u || !v || !level || !valid || !mp_desc || !scale_factors) return matcher_fail(UVO_E_BADARG, "null pointer");
+  if (!assigned || !u || !v || !level || !valid || !mp_desc || !scale_factors) return fail(UVO_E_BADARG, "null pointer");
   std::vector<float> r(nmp, 0.f);
   std::vector<int32_t> lo(nmp, 0), hi(nmp, 0), match(nmp, -1);
   std::vector<uint8_t> blocked(n);
   for (int i = 0; i < nmp; ++i) {
     if (!valid[i]) continue;
-    if (level[i] < 0 || level[i] >= nlevels) return matcher_fail(UVO_E_BADARG, "map point level outside 0..nlevels-1");
+    if (level[i] < 0 || level[i] >= nlevels) return fail(UVO_E_BADARG, "map point level outside 0..nlevels-1");
     r[i] = th * scale_factors[level[i]];                // :1672
     lo[i] = level[i] - 1, hi[i] = level[i] + 1;         // :1674
   }
@@ -313,15 +218,15 @@ int uvo_search_by_projection_kf(uvo_matcher* m, const uvo_keypoint* kp, int n, c
 int uvo_fuse(uvo_matcher* m, const uvo_keypoint* kp, int n, const uint8_t* desc, int min_x, int min_y, int max_x, int max_y, int nmp,
              const float* u, const float* v, const int32_t* level, const uint8_t* valid, const uint8_t* mp_desc, const float* scale_factors,
              int nlevels, float th, int32_t* best_idx, int32_t* best_dist) {
-  if (!m) return matcher_fail(UVO_E_BADARG, "null handle");
-  if (n < 0 || nmp < 0 || nlevels < 1) return matcher_fail(UVO_E_BADARG, "bad sizes");
+  if (!m) return fail(UVO_E_BADARG, "null handle");
+  if (n < 0 || nmp < 0 || nlevels < 1) return fail(UVO_E_BADARG, "bad sizes");
   if (nmp == 0) return UVO_OK;
-  if (!best_idx || !best_dist || !u || !v || !level || !valid || !mp_desc || !scale_factors) return matcher_fail(UVO_E_BADARG, "null pointer");
+  if (!best_idx || !best_dist || !u || !v || !level || !valid || !mp_desc || !scale_factors) return fail(UVO_E_BADARG, "null pointer");
   std::vector<float> r(nmp, 0.f);
   std::vector<int32_t> lo(nmp, 0), hi(nmp, 0);
   for (int i = 0; i < nmp; ++i) {
     if (!valid[i]) continue;
-    if (level[i] < 0 || level[i] >= nlevels) return matcher_fail(UVO_E_BADARG, "map point level outside 0..nlevels-1");
+    if (level[i] < 0 || level[i] >= nlevels) return fail(UVO_E_BADARG, "map point level outside 0..nlevels-1");
     r[i] = th * scale_factors[level[i]];         // :1077
     lo[i] = level[i] - 1, hi[i] = level[i];      // :1094
   }
@@ -334,11 +239,11 @@ int uvo_fuse(uvo_matcher* m, const uvo_keypoint* kp, int n, const uint8_t* desc,
 int uvo_search_by_bow(uvo_matcher* m, int kf_kf, const uvo_feature_vector* fv1, int n1, const uint8_t* desc1, const float* angle1,
                       const uint8_t* usable1, const uvo_feature_vector* fv2, int n2, const uint8_t* desc2, const float* angle2,
                       const uint8_t* usable2, float nnratio, int check_orientation, int32_t* match12, int* n_matches) {
-  if (!m || !n_matches) return matcher_fail(UVO_E_BADARG, "null pointer");
+  if (!m || !n_matches) return fail(UVO_E_BADARG, "null pointer");
   *n_matches = 0;
-  if (n1 < 0 || n2 < 0) return matcher_fail(UVO_E_BADARG, "bad sizes");
+  if (n1 < 0 || n2 < 0) return fail(UVO_E_BADARG, "bad sizes");
   if (n1 == 0) return UVO_OK;
-  if (!match12 || !usable1) return matcher_fail(UVO_E_BADARG, "null pointer");
+  if (!match12 || !usable1) return fail(UVO_E_BADARG, "null pointer");
   for (int i = 0; i < n1; ++i) match12[i] = -1;
   RC(check_fv(fv1, n1));
   RC(check_fv(fv2, n2));
@@ -379,16 +284,16 @@ int uvo_search_for_triangulation(uvo_matcher* m, const uvo_feature_vector* fv1, 
                                  const uint8_t* has_mp1, const uvo_feature_vector* fv2, const uvo_keypoint* kp2, int n2, const uint8_t* desc2,
                                  const uint8_t* has_mp2, const float* f12, const float* sigma2, int nlevels, int check_orientation,
                                  int32_t* match12, int* n_matches) {
-  if (!m || !n_matches) return matcher_fail(UVO_E_BADARG, "null pointer");
+  if (!m || !n_matches) return fail(UVO_E_BADARG, "null pointer");
   *n_matches = 0;
-  if (n1 < 0 || n2 < 0 || nlevels < 1) return matcher_fail(UVO_E_BADARG, "bad sizes");
+  if (n1 < 0 || n2 < 0 || nlevels < 1) return fail(UVO_E_BADARG, "bad sizes");
   if (n1 == 0) return UVO_OK;
-  if (!match12 || !kp1 || !desc1 || !has_mp1 || !f12 || !sigma2) return matcher_fail(UVO_E_BADARG, "null pointer");
+  if (!match12 || !kp1 || !desc1 || !has_mp1 || !f12 || !sigma2) return fail(UVO_E_BADARG, "null pointer");
   for (int i = 0; i < n1; ++i) match12[i] = -1;
   RC(check_fv(fv1, n1));
   RC(check_fv(fv2, n2));
   if (n2 == 0) return UVO_OK;
-  if (!kp2 || !desc2 || !has_mp2) return matcher_fail(UVO_E_BADARG, "null pointer");
+  if (!kp2 || !desc2 || !has_mp2) return fail(UVO_E_BADARG, "null pointer");
   std::vector<int32_t> q_of, start(1, 0), cidx;
   for_shared_nodes(fv1, fv2, [&](int a, int b) {
     for (int e = fv1->start[a]; e < fv1->start[a + 1]; ++e) {
@@ -425,17 +330,17 @@ int uvo_project_points(uvo_matcher* m, int mode, const uvo_camera_pose* cam, int
                        const float* min_distance_inv, const float* max_distance_inv, const float* max_distance, const uint8_t* usable,
                        const float* scale_factors, int nlevels, float scale_factor, float viewing_cos_limit, uint8_t* valid, float* u, float* v,
                        int32_t* level, float* view_cos) {
-  if (!m || !cam) return matcher_fail(UVO_E_BADARG, "null pointer");
-  if (mode < UVO_PROJECT_FRUSTUM || mode > UVO_PROJECT_PIXEL) return matcher_fail(UVO_E_BADARG, "unknown projection mode");
+  if (!m || !cam) return fail(UVO_E_BADARG, "null pointer");
+  if (mode < UVO_PROJECT_FRUSTUM || mode > UVO_PROJECT_PIXEL) return fail(UVO_E_BADARG, "unknown projection mode");
   const bool pixel_only = mode == UVO_PROJECT_PIXEL || mode == UVO_PROJECT_PIXEL_BOUNDED;  // u, v and at most the image-bounds test
-  if (npts < 0 || nlevels < 1 || nlevels > 64) return matcher_fail(UVO_E_BADARG, "bad sizes");
+  if (npts < 0 || nlevels < 1 || nlevels > 64) return fail(UVO_E_BADARG, "bad sizes");
   if (npts == 0) return UVO_OK;
-  if (!xyz || !scale_factors || !valid || !u || !v || !level) return matcher_fail(UVO_E_BADARG, "null pointer");
-  if (!pixel_only && !min_distance_inv) return matcher_fail(UVO_E_BADARG, "this mode needs the minimum invariance distance");
-  if (!pixel_only && mode != UVO_PROJECT_KF_RELOC && !max_distance_inv) return matcher_fail(UVO_E_BADARG, "this mode needs the maximum invariance distance");
-  if (mode == UVO_PROJECT_FRUSTUM && !max_distance) return matcher_fail(UVO_E_BADARG, "PredictScale needs the raw mfMaxDistance");
-  if (!pixel_only && mode != UVO_PROJECT_KF_RELOC && !normal) return matcher_fail(UVO_E_BADARG, "this mode needs the point normals");
-  if (mode == UVO_PROJECT_FRUSTUM && !(scale_factor > 1.0f)) return matcher_fail(UVO_E_BADARG, "scale_factor must be > 1");
+  if (!xyz || !scale_factors || !valid || !u || !v || !level) return fail(UVO_E_BADARG, "null pointer");
+  if (!pixel_only && !min_distance_inv) return fail(UVO_E_BADARG, "this mode needs the minimum invariance distance");
+  if (!pixel_only && mode != UVO_PROJECT_KF_RELOC && !max_distance_inv) return fail(UVO_E_BADARG, "this mode needs the maximum invariance distance");
+  if (mode == UVO_PROJECT_FRUSTUM && !max_distance) return fail(UVO_E_BADARG, "PredictScale needs the raw mfMaxDistance");
+  if (!pixel_only && mode != UVO_PROJECT_KF_RELOC && !normal) return fail(UVO_E_BADARG, "this mode needs the point normals");
+  if (mode == UVO_PROJECT_FRUSTUM && !(scale_factor > 1.0f)) return fail(UVO_E_BADARG, "scale_factor must be > 1");
   UVO_HIP_CHECK(hipSetDevice(m->device));
   hipStream_t s = m->stream;
   float *d_xyz, *d_normal = nullptr, *d_min = nullptr, *d_max = nullptr, *d_max_raw = nullptr, *d_sf, *d_u;
@@ -469,11 +374,11 @@ int uvo_project_points(uvo_matcher* m, int mode, const uvo_camera_pose* cam, int
 // convertTo(alpha = 1./scw), whose 32F kernel multiplies by (float)alpha; `-Rcw.t() * tcw` is gemm(GEMM_1_T, alpha = -1): general
 // path, double accumulation.
 int uvo_sim3_decompose(const float* scw_mat, int row_stride, uvo_camera_pose* cam) {
-  if (!scw_mat || !cam || row_stride < 4) return matcher_fail(UVO_E_BADARG, "null pointer / row_stride < 4");
+  if (!scw_mat || !cam || row_stride < 4) return fail(UVO_E_BADARG, "null pointer / row_stride < 4");
   double dot = 0.0;
   for (int k = 0; k < 3; ++k) dot += (double)scw_mat[k] * (double)scw_mat[k];
   const float scw = (float)std::sqrt(dot);
-  if (!(scw > 0.f)) return matcher_fail(UVO_E_BADARG, "Scw has a zero first row");
+  if (!(scw > 0.f)) return fail(UVO_E_BADARG, "Scw has a zero first row");
   const float inv = (float)(1.0 / (double)scw);
   for (int i = 0; i < 3; ++i) {
     for (int j = 0; j < 3; ++j) cam->rcw[3 * i + j] = scw_mat[i * row_stride + j] * inv;
@@ -490,8 +395,8 @@ int uvo_sim3_decompose(const float* scw_mat, int row_stride, uvo_camera_pose* ca
 // src/ORBmatcher.cc:1284-1287: `s12*R12` and `(1.0/s12)*R12.t()` are convertTo with (float)alpha; `-sR21*t12` is the small-matrix
 // gemm: fp32 row sum, times alpha = -1 in double
 int uvo_sim3_relative(float s12, const float* r12, const float* t12, float* s_r12, float* s_r21, float* t21) {
-  if (!r12 || !t12 || !s_r12 || !s_r21 || !t21) return matcher_fail(UVO_E_BADARG, "null pointer");
-  if (!(s12 > 0.f)) return matcher_fail(UVO_E_BADARG, "s12 must be positive");
+  if (!r12 || !t12 || !s_r12 || !s_r21 || !t21) return fail(UVO_E_BADARG, "null pointer");
+  if (!(s12 > 0.f)) return fail(UVO_E_BADARG, "s12 must be positive");
   for (int i = 0; i < 9; ++i) s_r12[i] = r12[i] * s12;
   const float inv = (float)(1.0 / (double)s12);
   for (int i = 0; i < 3; ++i)
@@ -506,11 +411,11 @@ int uvo_sim3_relative(float s12, const float* r12, const float* t12, float* s_r1
 int uvo_project_sim3(uvo_matcher* m, const float* r_own, const float* t_own, const float* s_r, const float* t, const uvo_camera_pose* cam_other,
                      int npts, const float* xyz, const float* min_distance_inv, const float* max_distance_inv, const uint8_t* usable,
                      const float* scale_factors, int nlevels, uint8_t* valid, float* u, float* v, int32_t* level) {
-  if (!m || !r_own || !t_own || !s_r || !t || !cam_other) return matcher_fail(UVO_E_BADARG, "null pointer");
-  if (npts < 0 || nlevels < 1 || nlevels > 64) return matcher_fail(UVO_E_BADARG, "bad sizes");
+  if (!m || !r_own || !t_own || !s_r || !t || !cam_other) return fail(UVO_E_BADARG, "null pointer");
+  if (npts < 0 || nlevels < 1 || nlevels > 64) return fail(UVO_E_BADARG, "bad sizes");
   if (npts == 0) return UVO_OK;
   if (!xyz || !min_distance_inv || !max_distance_inv || !scale_factors || !valid || !u || !v || !level)
-    return matcher_fail(UVO_E_BADARG, "null pointer");
+    return fail(UVO_E_BADARG, "null pointer");
   UVO_HIP_CHECK(hipSetDevice(m->device));
   hipStream_t s = m->stream;
   float *d_xyz, *d_min, *d_max, *d_sf, *d_u;
@@ -537,17 +442,17 @@ int uvo_project_sim3(uvo_matcher* m, const float* r_own, const float* t_own, con
 int uvo_search_by_projection_sim3(uvo_matcher* m, const uvo_keypoint* kp, int n, const uint8_t* desc, int min_x, int min_y, int max_x, int max_y,
                                   int32_t* matched, int nmp, const float* u, const float* v, const int32_t* level, const uint8_t* valid,
                                   const uint8_t* mp_desc, const float* scale_factors, int nlevels, int th, int* n_matches) {
-  if (!m || !n_matches) return matcher_fail(UVO_E_BADARG, "null pointer");
+  if (!m || !n_matches) return fail(UVO_E_BADARG, "null pointer");
   *n_matches = 0;
-  if (n < 0 || nmp < 0 || nlevels < 1) return matcher_fail(UVO_E_BADARG, "bad sizes");
+  if (n < 0 || nmp < 0 || nlevels < 1) return fail(UVO_E_BADARG, "bad sizes");
   if (n == 0 || nmp == 0) return UVO_OK;
-  if (!matched || !u || !v || !level || !valid || !mp_desc || !scale_factors) return matcher_fail(UVO_E_BADARG, "null pointer");
+  if (!matched || !u || !v || !level || !valid || !mp_desc || !scale_factors) return fail(UVO_E_BADARG, "null pointer");
   std::vector<float> r(nmp, 0.f);
   std::vector<int32_t> lo(nmp, 0), hi(nmp, 0), match(nmp, -1);
   std::vector<uint8_t> blocked(n);
   for (int i = 0; i < nmp; ++i) {
     if (!valid[i]) continue;
-    if (level[i] < 0 || level[i] >= nlevels) return matcher_fail(UVO_E_BADARG, "map point level outside 0..nlevels-1");
+    if (level[i] < 0 || level[i] >= nlevels) return fail(UVO_E_BADARG, "map point level outside 0..nlevels-1");
     r[i] = th * scale_factors[level[i]];      // :357 (int th promoted to float)
     lo[i] = level[i] - 1, hi[i] = level[i];   // :377
   }
@@ -566,16 +471,16 @@ int uvo_search_by_sim3(uvo_matcher* m, const uvo_keypoint* kp1, int n1, const ui
                        const uint8_t* valid12, const uint8_t* mp_desc1, const float* u21, const float* v21, const int32_t* level21,
                        const uint8_t* valid21, const uint8_t* mp_desc2, const float* scale_factors1, int nlevels1, const float* scale_factors2,
                        int nlevels2, float th, int32_t* match12, int* n_found) {
-  if (!m || !n_found) return matcher_fail(UVO_E_BADARG, "null pointer");
+  if (!m || !n_found) return fail(UVO_E_BADARG, "null pointer");
   *n_found = 0;
-  if (n1 < 0 || n2 < 0 || nlevels1 < 1 || nlevels2 < 1) return matcher_fail(UVO_E_BADARG, "bad sizes");
+  if (n1 < 0 || n2 < 0 || nlevels1 < 1 || nlevels2 < 1) return fail(UVO_E_BADARG, "bad sizes");
   if (n1 == 0) return UVO_OK;
-  if (!match12) return matcher_fail(UVO_E_BADARG, "null pointer");
+  if (!match12) return fail(UVO_E_BADARG, "null pointer");
   for (int i = 0; i < n1; ++i) match12[i] = -1;
   if (n2 == 0) return UVO_OK;
   if (!bounds1 || !bounds2 || !u12 || !v12 || !level12 || !valid12 || !mp_desc1 || !u21 || !v21 || !level21 || !valid21 || !mp_desc2 ||
       !scale_factors1 || !scale_factors2)
-    return matcher_fail(UVO_E_BADARG, "null pointer");
+    return fail(UVO_E_BADARG, "null pointer");
   // one direction: queries = the projected map points, targets = the other key frame's key points (:1361-1394 / :1443-1476)
   auto direction = [&](const uvo_keypoint* kp, int n, const uint8_t* desc, const int32_t* b, int nq, const float* u, const float* v,
                        const int32_t* level, const uint8_t* valid, const uint8_t* qdesc, const float* sf, int nl, std::vector<int32_t>& out) -> int {
@@ -583,7 +488,7 @@ int uvo_search_by_sim3(uvo_matcher* m, const uvo_keypoint* kp1, int n1, const ui
     std::vector<int32_t> lo(nq, 0), hi(nq, 0);
     for (int i = 0; i < nq; ++i) {
       if (!valid[i]) continue;
-      if (level[i] < 0 || level[i] >= nl) return matcher_fail(UVO_E_BADARG, "map point level outside 0..nlevels-1");
+      if (level[i] < 0 || level[i] >= nl) return fail(UVO_E_BADARG, "map point level outside 0..nlevels-1");
       r[i] = th * sf[level[i]];
       lo[i] = level[i] - 1, hi[i] = level[i];
     }
@@ -606,13 +511,13 @@ int uvo_search_by_sim3(uvo_matcher* m, const uvo_keypoint* kp1, int n1, const ui
 }
 
 int uvo_haloc_hash(uvo_matcher* m, const float* proj, int num_proj, int proj_stride, const uint8_t* desc, int n, float* hash) {
-  if (!m || !hash) return matcher_fail(UVO_E_BADARG, "null pointer");
-  if (num_proj < 1 || n < 0 || proj_stride < n) return matcher_fail(UVO_E_BADARG, "bad sizes (proj_stride must cover the descriptor rows)");
+  if (!m || !hash) return fail(UVO_E_BADARG, "null pointer");
+  if (num_proj < 1 || n < 0 || proj_stride < n) return fail(UVO_E_BADARG, "bad sizes (proj_stride must cover the descriptor rows)");
   if (n == 0) {  // :66 the zero-initialised histogram
     for (int k = 0; k < num_proj * 32; ++k) hash[k] = 0.0f;
     return UVO_OK;
   }
-  if (!proj || !desc) return matcher_fail(UVO_E_BADARG, "null pointer");
+  if (!proj || !desc) return fail(UVO_E_BADARG, "null pointer");
   UVO_HIP_CHECK(hipSetDevice(m->device));
   hipStream_t s = m->stream;
   float *d_proj, *d_hash;
