@@ -20,6 +20,10 @@
  *   SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th)             :1267-1505
  * the two loops of the LocalMapping thread in batched form (one device round trip per loop instead of one to three per key frame):
  *   SearchForTriangulationBegin / SearchForTriangulationNext             the loop of src/LocalMapping.cc:1058-1080
+ *     Contract: the batch of the last successful Begin survives every other member called in between, including one that grows the
+ *     device handle (more key points or map points than any call before): the handle that holds the batch is kept for Next until the
+ *     next Begin or the destructor, and the other members get a new one.  A Next without a successful Begin returns 0 and sets
+ *     last_error().
  *   FuseTargets(vpTargetKFs, vpMapPoints, th)                            the loop of src/LocalMapping.cc:1228-1236
  * and the four members nothing in the reference calls (kept so that the class is complete):
  *   WindowSearch(F1, F2, windowSize, vpMapPointMatches2, minOctave, maxOctave)   :409-516
@@ -56,7 +60,10 @@ class UVO_COMPAT_MATCHER_NAME {
   static const int TH_LOW = 50, TH_HIGH = 100, HISTO_LENGTH = 30;  // src/ORBmatcher.cc:40-42
 
   UVO_COMPAT_MATCHER_NAME(float nnratio = 0.6, bool checkOri = true) : mfNNratio(nnratio), mbCheckOrientation(checkOri) {}
-  ~UVO_COMPAT_MATCHER_NAME() { uvo_matcher_destroy(m_); }
+  ~UVO_COMPAT_MATCHER_NAME() {
+    if (tri_ != m_) uvo_matcher_destroy(tri_);
+    uvo_matcher_destroy(m_);
+  }
   UVO_COMPAT_MATCHER_NAME(const UVO_COMPAT_MATCHER_NAME&) = delete;
   UVO_COMPAT_MATCHER_NAME& operator=(const UVO_COMPAT_MATCHER_NAME&) = delete;
 
@@ -394,6 +401,8 @@ class UVO_COMPAT_MATCHER_NAME {
     uvo_feature_vector c1 = f1.c();
     const int rc = uvo_search_for_triangulation_batch(m_, &c1, reinterpret_cast<const uvo_keypoint*>(vKeysUn1.data()), n1, d1.data(), has1.data(), np,
                                                       pairs.data());
+    if (tri_ != m_) uvo_matcher_destroy(tri_);  // a new batch replaces the old one, on whichever handle it lives
+    tri_ = rc == UVO_OK ? m_ : nullptr;
     if (rc != UVO_OK) err_ = uvo_last_error();
     return rc;
   }
@@ -408,7 +417,11 @@ class UVO_COMPAT_MATCHER_NAME {
     for (int i = 0; i < n1; ++i) has1[i] = vpMapPoints1[i] != NULL;
     std::vector<int32_t> match(n1, -1);
     int nmatches = 0;
-    if (uvo_search_for_triangulation_next(m_, k, has1.data(), mbCheckOrientation ? 1 : 0, match.data(), &nmatches) != UVO_OK) {
+    if (!tri_) {
+      err_ = "SearchForTriangulationNext without a successful SearchForTriangulationBegin";
+      return 0;
+    }
+    if (uvo_search_for_triangulation_next(tri_, k, has1.data(), mbCheckOrientation ? 1 : 0, match.data(), &nmatches) != UVO_OK) {
       err_ = uvo_last_error();
       return 0;
     }
@@ -956,7 +969,7 @@ class UVO_COMPAT_MATCHER_NAME {
   }
   int ensure(int n, int nmp) {
     if (m_ && n <= cap_n_ && nmp <= cap_mp_) return UVO_OK;
-    uvo_matcher_destroy(m_);
+    if (m_ != tri_) uvo_matcher_destroy(m_);  // the handle of a live triangulation batch stays with tri_ (see the header comment)
     m_ = nullptr;
     cap_n_ = n > cap_n_ ? 2 * n : cap_n_;
     cap_mp_ = nmp > cap_mp_ ? 2 * nmp : cap_mp_;
@@ -970,6 +983,7 @@ class UVO_COMPAT_MATCHER_NAME {
     return rc;
   }
   uvo_matcher* m_ = nullptr;
+  uvo_matcher* tri_ = nullptr;  // the handle that holds the batch of the last successful SearchForTriangulationBegin (m_ or an older one)
   int cap_n_ = 0, cap_mp_ = 0, device_ = 0;
   std::string err_;
 };

@@ -505,3 +505,57 @@ def test_projection_searches_between_two_frames(oracle):
     n = oracle.search_by_projection_last(cam, kp2, d2, a, np.ones(3, np.uint8), xyz2, np.array([0, 1, 0], np.int32), np.zeros(3, np.float32), d1, sf, 3.0,
                                          False)
     assert n == 2 and a.tolist() == [0, 1, -1]
+
+
+def test_fuse_map_model_by_hand():
+    """tests/compat_model.py, the map model behind the expected values of the compat-adaptor scenes, on a hand-worked example: the loop of
+    LocalMapping::SearchInNeighbors (one Fuse per target, src/LocalMapping.cc:1228-1236) with a Replace that re-describes a point the next
+    target then finds only with its new descriptor, the tie rule of ComputeDistinctiveDescriptors, and Fuse(pKF, Scw) replacing the other way."""
+    import compat_model as cm
+
+    def bits(lo, k):                       # descriptor with bits [lo, lo + k) set: distance(bits(lo, a), bits(lo, b)) = |a - b|
+        u = np.zeros(256, np.uint8)
+        u[lo:lo + k] = 1
+        return np.packbits(u)
+    d, e, f = (lambda k: bits(0, k)), (lambda k: bits(64, k)), (lambda k: bits(128, k))
+
+    def search(model):                     # the window search stripped to its descriptor rule: nearest key point within TH_LOW
+        def s(kf, p):
+            dist = [cm.descriptor_distance(p.desc, x) for x in model.kfs[kf].desc]
+            return int(np.argmin(dist)) if min(dist) <= 50 else -1
+        return s
+
+    def scene():
+        kfs = [cm.KeyFrame([d(20), d(6), f(0), d(40), e(9)], [0, 1, 2, 3, -1]),     # the current key frame: p0 p1 p2 p3(bad) NULL
+               cm.KeyFrame([d(4), f(2)], [0, -1]),                                  # target 1 holds p0
+               cm.KeyFrame([d(22), f(5)], [-1, 5])]                                 # target 2 holds p5
+        pts = [cm.MapPoint(0, e(60)), cm.MapPoint(1, d(6)), cm.MapPoint(2, f(3)), cm.MapPoint(3, d(40), bad=True), cm.MapPoint(4, e(55)),
+               cm.MapPoint(5, f(5))]
+        return cm.MapModel(kfs, pts)
+
+    m = scene()
+    assert m.mps[0].obs == {0: 0, 1: 0} and m.mps[3].obs == {} and m.mps[5].obs == {2: 1}
+    n = m.fuse_targets([1, 2], [0, 1, 2, 3, -1], search(m))
+    # target 1: p0 is in it; p1 finds p0's key point -> p1.Replace(p0): p0 already observes key frame 0, so p1's slot there is erased,
+    #           and p0's descriptor becomes the first of {kf0: d(20), kf1: d(4)} (two descriptors: both medians 0, the first wins);
+    #           p2 finds the free key point 1 -> observation.
+    # target 2: p0 now finds key point 0 (d(20) vs d(22); its old e(60) was 82 away); p1 is bad now; p2 finds p5's key point ->
+    #           p2.Replace(p5): p5 takes over kf0:2 and kf1:1, descriptor = median of {f(0), f(2), f(5)}: medians 2, 2, 3 -> f(0), the first.
+    assert n == 4
+    assert m.counts == {"fuse_targets:replace": 2, "fuse_targets:add": 2, "fuse_targets:redescribed_searched": 1, "fuse_targets:redescribed_changed": 1}
+    kfs, mps = m.dump()
+    assert kfs == {0: [0, -1, 5, 3, -1], 1: [0, 5], 2: [0, 5]}
+    assert mps[0] == (0, -1, [(0, 0), (1, 0), (2, 0)], d(20).tobytes().hex())
+    assert mps[1] == (1, 0, [], d(6).tobytes().hex())
+    assert mps[2] == (1, 5, [], f(3).tobytes().hex())
+    assert mps[3] == (1, -1, [], d(40).tobytes().hex())
+    assert mps[5] == (0, -1, [(0, 2), (1, 1), (2, 1)], f(0).tobytes().hex())
+    # without the re-description p0 would not have been fused into target 2: the stale descriptor misses it
+    m2 = scene()
+    assert search(m2)(2, m2.mps[0]) == -1
+    # Fuse(pKF, Scw, ...): the key frame's point is the one replaced (src/ORBmatcher.cc:1247-1252); p1 is candidate, p0 sits in target 1
+    m3 = scene()
+    assert m3.fuse_scw(1, [1, 4], search(m3)) == 1
+    kfs, mps = m3.dump()
+    assert kfs[0] == [-1, 1, 2, 3, -1] and kfs[1] == [1, -1]
+    assert mps[0][:3] == (1, 1, []) and mps[1] == (0, -1, [(0, 1), (1, 0)], d(6).tobytes().hex())
