@@ -768,6 +768,40 @@ int uvo_undistort_points(uvo_klt* k, const uvo_camera_model* cam, const float* p
 int uvo_klt_track_undistorted(uvo_klt* k, int prev_slot, int next_slot, const float* prev_pts, float* next_pts, int n, int max_level, int max_count,
                               double epsilon, double min_eig_threshold, const uvo_camera_model* cam, uint8_t* status, float* err, float* prev_un,
                               float* next_un);
+/*
+ * cv::findFundamentalMat(pts0_Un, pts1_Un, cv::FM_RANSAC, thr, conf, mask_rsc) (src/Tracking.cc:1062, thr 1, conf 0.999) on the device, in
+ * the handle's stream, scratch sized at uvo_klt_create (n <= max_points; nothing allocated per call).  OpenCV 3.4's semantics, recalled
+ * [OCV-RECALL, listed in tests/fundamental_model.py]: thr <= 0 -> 3 and conf outside (DBL_EPSILON, 1 - DBL_EPSILON) -> 0.99 (NaN in
+ * either: UVO_E_BADARG); n < 7 no model; n == 7 the 7-point kernel once, mask all 1; 8..14 points LMedS; from 15 points RANSAC
+ * (cv::RNG seeded with (uint64)-1, at most 1000 hypotheses).  Host buffers p0, p1: n x (x, y) float32.
+ *   mask : n bytes, always written -- all 0 where OpenCV leaves the mask empty
+ *   F    : 9 doubles, row-major (may be NULL): the model OpenCV returns (the first of the n == 7 kernel's), zeros where it returns none
+ *   info : may be NULL
+ * Tolerance contract: RNG stream, subsets, inlier counts, the chosen model, the iteration count and the mask are
+ * exact, F agrees within 1e-6 (the null-space basis differs from OpenCV's SVD), with two stated exceptions.
+ */
+#define UVO_FM_NONE 0
+#define UVO_FM_SEVEN_POINT 1
+#define UVO_FM_RANSAC 2
+#define UVO_FM_LMEDS 3
+typedef struct uvo_fm_info {
+  int32_t method;      /* UVO_FM_* */
+  int32_t iterations;  /* OpenCV's iter at loop exit (0 for n <= 7) */
+  int32_t inliers;     /* mask bytes set */
+  uint32_t rng_draws;  /* cv::RNG::next() calls consumed */
+} uvo_fm_info;
+int uvo_klt_find_fundamental(uvo_klt* k, const float* p0, const float* p1, int n, double thr, double conf, uint8_t* mask, double* F,
+                             uvo_fm_info* info);
+/* Tracking::perform_matching from :1037 on in one call, one upload and one download: n < 10 -> mask_out all 0, F zeros, nothing else is
+ * touched and the tracker does not run; otherwise uvo_klt_track_undistorted, then findFundamentalMat on all n undistorted pairs (lost
+ * points included, wherever the tracker left them) and mask_out[i] = status[i] && inlier[i].  F may be NULL. */
+int uvo_klt_track_filtered(uvo_klt* k, int prev_slot, int next_slot, const float* prev_pts, float* next_pts, int n, int max_level, int max_count,
+                           double epsilon, double min_eig_threshold, const uvo_camera_model* cam, uint8_t* status, float* err, float* prev_un,
+                           float* next_un, double thr, double conf, uint8_t* mask_out, double* F);
+/* test tap: the hypotheses of the handle's last findFundamentalMat call, in draw order, up to its iterations: subsets [cap][7] point
+ * indices, n_models [cap] (<= 0: the 7-point kernel gave none), scores [cap][3] (inlier counts, or LMedS medians; -1 where no model).
+ * *n = hypotheses written. */
+int uvo_klt_fm_hypotheses(uvo_klt* k, int32_t* subsets, int32_t* n_models, double* scores, int cap, int* n);
 
 /* last HIP / argument error text for the calling thread's most recent failing call (never NULL) */
 const char* uvo_last_error(void);

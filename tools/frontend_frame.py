@@ -3,7 +3,9 @@
 fastTh 20, Px_distance 20): CLAHE -> optical-flow pyramid -> Lucas-Kanade tracking of the previous frame's points -> top-up ORB
 extraction (tracked points pass through, the occupancy grid keeps new detections away from them).  Every stage on the GPU through
 the C ABI; per-stage wall-clock (host buffers in/out) and a check of the final keypoints / descriptors against the oracle fed with
-the same tracked points.  Prints one JSON object."""
+the same tracked points.  The RANSAC stage of perform_matching (src/Tracking.cc:1062) is timed through the fused call
+(uvo_klt_track_filtered: tracker + undistortion + findFundamentalMat) on the same points, beside the chain: "track_filtered" is its
+wall-clock, "total_with_ransac" the frame with it in place of the plain tracker call.  Prints one JSON object."""
 import importlib
 import json
 import os
@@ -32,6 +34,7 @@ def main():
     ex = uvo.ORBextractor(NF, 1.2, 8, 0, 20, max_width=W, max_height=H, max_input_keypoints=4096)
     oe = o.extractor(NF, 1.2, 8, 20)
     klt = uvo.KLT(W, H, (21, 21), 5, max_points=4096, slots=2)
+    cam = uvo.CameraModel.make(0.9 * W, 0.9 * W, W / 2, H / 2, [])
     res = {}
     if os.environ.get("UVO_FF_PROFILE"):
         ex.profile(True)
@@ -43,6 +46,7 @@ def main():
         # "chain": the enhanced frame stays in HBM between the three calls (clahe without download, pyramid and extraction from it)
         chain = check == "chain"
         t = {"clahe": [], "pyramid": [], "track": [], "extract": []}
+        tf, nin = [], []
         prev_pts = None
         for i, raw in enumerate(frames):
             t0 = time.perf_counter()
@@ -71,6 +75,11 @@ def main():
             t4 = time.perf_counter()
             kp, de = ex(img, kin_gpu, g_gpu, MINPX, i == 0, need)
             t5 = time.perf_counter()
+            if prev_pts is not None and len(prev_pts) >= 10:     # the fused call on the same points, outside the chain
+                t6 = time.perf_counter()
+                f = klt.track_filtered((i - 1) & 1, i & 1, prev_pts, cam)
+                tf.append(time.perf_counter() - t6)
+                nin.append(int(f[5].sum()))
             if i >= 3:
                 t["clahe"].append(t1 - t0), t["pyramid"].append(t2 - t1), t["track"].append(t3 - t2), t["extract"].append(t5 - t4)
             if check:   # both the idle-GPU pass and the chained pass are checked against the oracle
@@ -80,6 +89,9 @@ def main():
         key = "hbm_chained_idle_gpu_between_frames" if chain else ("idle_gpu_between_frames" if check else "back_to_back")
         res[key] = {k: round(float(np.median(v)) * 1e3, 3) for k, v in t.items()}
         res[key]["total"] = round(float(sum(np.median(v) for v in t.values())) * 1e3, 3)
+        res[key]["track_filtered"] = round(float(np.median(tf[2:])) * 1e3, 3)
+        res[key]["total_with_ransac"] = round(res[key]["total"] + res[key]["track_filtered"] - res[key]["track"], 3)
+        res[key]["mean_ransac_inliers"] = round(float(np.mean(nin)), 1)
     out = {"workload": "640x512 sequence of 21 frames, CLAHE(4, 12x12) + KLT(21x21, 5 levels) + top-up ORB (1000 feats, fastTh 20, Px_distance 20)",
            "ms_per_frame": res,
            "mean_tracked_points": round(float(np.mean(ntracked)), 1),

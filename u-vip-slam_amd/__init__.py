@@ -42,7 +42,7 @@ ABI_SYMBOLS = [
     "uvo_grider_fast", "uvo_clahe", "uvo_clahe_batch_device", "uvo_extractor_read_plane", "uvo_extractor_read_candidates", "uvo_extractor_profile", "uvo_extractor_profile_only", "uvo_extractor_kernel_times",
     "uvo_matcher_create", "uvo_matcher_destroy", "uvo_matcher_synchronize", "uvo_hamming_knn2", "uvo_hamming_knn2_batch_device",
     "uvo_hamming_matrix", "uvo_distinctive_descriptors", "uvo_search_by_projection", "uvo_match_windows", "uvo_match_groups",
-    "uvo_search_by_projection_kf", "uvo_search_by_bow", "uvo_search_for_triangulation", "uvo_search_for_triangulation_batch", "uvo_search_for_triangulation_next", "uvo_fuse", "uvo_fuse_batch", "uvo_project_points", "uvo_search_points_in_frustum", "uvo_sim3_decompose", "uvo_sim3_relative", "uvo_project_sim3", "uvo_search_by_projection_sim3", "uvo_search_by_sim3", "uvo_haloc_hash", "uvo_klt_create", "uvo_klt_destroy", "uvo_klt_build_pyramid", "uvo_klt_build_pyramid_from_extractor", "uvo_klt_read_level", "uvo_klt_track", "uvo_undistort_points", "uvo_klt_track_undistorted", "uvo_vocabulary_create", "uvo_vocabulary_destroy", "uvo_bow_transform", "uvo_matcher_wait_extractor", "uvo_extractor_wait_matcher", "uvo_matcher_attach_extractor", "uvo_matcher_profile",
+    "uvo_search_by_projection_kf", "uvo_search_by_bow", "uvo_search_for_triangulation", "uvo_search_for_triangulation_batch", "uvo_search_for_triangulation_next", "uvo_fuse", "uvo_fuse_batch", "uvo_project_points", "uvo_search_points_in_frustum", "uvo_sim3_decompose", "uvo_sim3_relative", "uvo_project_sim3", "uvo_search_by_projection_sim3", "uvo_search_by_sim3", "uvo_haloc_hash", "uvo_klt_create", "uvo_klt_destroy", "uvo_klt_build_pyramid", "uvo_klt_build_pyramid_from_extractor", "uvo_klt_read_level", "uvo_klt_track", "uvo_undistort_points", "uvo_klt_track_undistorted", "uvo_klt_find_fundamental", "uvo_klt_track_filtered", "uvo_klt_fm_hypotheses", "uvo_vocabulary_create", "uvo_vocabulary_destroy", "uvo_bow_transform", "uvo_matcher_wait_extractor", "uvo_extractor_wait_matcher", "uvo_matcher_attach_extractor", "uvo_matcher_profile",
     "uvo_matcher_kernel_times", "uvo_last_error", "uvo_device_info",
 ]
 
@@ -223,6 +223,10 @@ def _load():
     lib.uvo_klt_track.argtypes = [vp, ci, ci, vp, vp, ci, ci, ci, ctypes.c_double, ctypes.c_double, vp, vp]
     lib.uvo_undistort_points.argtypes = [vp, vp, vp, ci, vp]
     lib.uvo_klt_track_undistorted.argtypes = [vp, ci, ci, vp, vp, ci, ci, ci, ctypes.c_double, ctypes.c_double, vp, vp, vp, vp, vp]
+    lib.uvo_klt_find_fundamental.argtypes = [vp, vp, vp, ci, ctypes.c_double, ctypes.c_double, vp, vp, vp]
+    lib.uvo_klt_track_filtered.argtypes = [vp, ci, ci, vp, vp, ci, ci, ci, ctypes.c_double, ctypes.c_double, vp, vp, vp, vp, vp, ctypes.c_double,
+                                           ctypes.c_double, vp, vp]
+    lib.uvo_klt_fm_hypotheses.argtypes = [vp, vp, vp, vp, ci, vp]
     lib.uvo_fuse.argtypes = [vp, vp, ci, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, ci, cf, vp, vp]
     lib.uvo_search_for_triangulation_batch.argtypes = [vp, vp, vp, ci, vp, vp, ci, vp]
     lib.uvo_search_for_triangulation_next.argtypes = [vp, ci, vp, ci, vp, vp]
@@ -1157,6 +1161,18 @@ class CameraModel(ctypes.Structure):
         return c
 
 
+UVO_FM_NONE, UVO_FM_SEVEN_POINT, UVO_FM_RANSAC, UVO_FM_LMEDS = 0, 1, 2, 3
+FM_MAX_HYPOTHESES = 1000
+
+
+class FmInfo(ctypes.Structure):
+    """uvo_fm_info."""
+    _fields_ = [("method", ctypes.c_int32), ("iterations", ctypes.c_int32), ("inliers", ctypes.c_int32), ("rng_draws", ctypes.c_uint32)]
+
+    def astuple(self):
+        return (self.method, self.iterations, self.inliers, self.rng_draws)
+
+
 class KltCfg(ctypes.Structure):
     """uvo_klt_cfg."""
     _fields_ = [("max_width", ctypes.c_int32), ("max_height", ctypes.c_int32), ("max_level", ctypes.c_int32), ("win_width", ctypes.c_int32),
@@ -1245,6 +1261,47 @@ class KLT:
         if rc:
             raise UvoError(rc, "uvo_klt_track_undistorted")
         return b, st, er, pu, nu
+
+    def find_fundamental(self, p0, p1, thr=1.0, conf=0.999):
+        """uvo_klt_find_fundamental: cv::findFundamentalMat(p0, p1, FM_RANSAC, thr, conf, mask) (src/Tracking.cc:1062) on the device.
+        Returns (mask uint8[n], F float64[3, 3] (zeros: no model), FmInfo)."""
+        a = np.ascontiguousarray(p0, np.float32).reshape(-1, 2)
+        b = np.ascontiguousarray(p1, np.float32).reshape(-1, 2)
+        if len(a) != len(b):
+            raise ValueError("p0 and p1 differ in length")
+        mask, F, info = np.zeros(len(a), np.uint8), np.zeros(9), FmInfo()
+        rc = lib.uvo_klt_find_fundamental(self._h, _ptr(a), _ptr(b), len(a), float(thr), float(conf), _ptr(mask), _ptr(F), ctypes.byref(info))
+        if rc:
+            raise UvoError(rc, "uvo_klt_find_fundamental")
+        return mask, F.reshape(3, 3), info
+
+    def track_filtered(self, prev_slot, next_slot, prev_pts, cam, next_pts0=None, thr=1.0, conf=0.999, want_F=True, max_count=30, epsilon=0.01,
+                       min_eig_threshold=1e-4, max_level=None):
+        """uvo_klt_track_filtered: Tracking::perform_matching from :1037 on (tracker, undistortion, findFundamentalMat, mask_out = status &&
+        inlier) in one call.  Returns (next, status, err, prev_un, next_un, mask_out, F or None); below 10 points only mask_out (all 0)
+        and F (zeros) are written."""
+        a = np.ascontiguousarray(prev_pts, np.float32).reshape(-1, 2)
+        b = a.copy() if next_pts0 is None else np.ascontiguousarray(next_pts0, np.float32).reshape(-1, 2).copy()
+        n = len(a)
+        st, er = np.zeros(n, np.uint8), np.zeros(n, np.float32)
+        pu, nu = np.zeros((n, 2), np.float32), np.zeros((n, 2), np.float32)
+        mask, F = np.zeros(n, np.uint8), (np.zeros(9) if want_F else None)
+        rc = lib.uvo_klt_track_filtered(self._h, prev_slot, next_slot, _ptr(a), _ptr(b), n, self._level(max_level), int(max_count), float(epsilon),
+                                        float(min_eig_threshold), ctypes.byref(cam), _ptr(st), _ptr(er), _ptr(pu), _ptr(nu), float(thr), float(conf),
+                                        _ptr(mask), _ptr(F))
+        if rc:
+            raise UvoError(rc, "uvo_klt_track_filtered")
+        return b, st, er, pu, nu, mask, (None if F is None else F.reshape(3, 3))
+
+    def fm_hypotheses(self):
+        """uvo_klt_fm_hypotheses: the last findFundamentalMat call's hypotheses in draw order -- (subsets int32[h, 7], n_models int32[h],
+        scores float64[h, 3]: inlier counts or LMedS medians, -1 where no model)."""
+        cap = FM_MAX_HYPOTHESES
+        sub, nm, sc, n = np.zeros((cap, 7), np.int32), np.zeros(cap, np.int32), np.zeros((cap, 3)), ctypes.c_int()
+        rc = lib.uvo_klt_fm_hypotheses(self._h, _ptr(sub), _ptr(nm), _ptr(sc), cap, ctypes.byref(n))
+        if rc:
+            raise UvoError(rc, "uvo_klt_fm_hypotheses")
+        return sub[:n.value].copy(), nm[:n.value].copy(), sc[:n.value].copy()
 
 
 def DescriptorDistance(a, b):

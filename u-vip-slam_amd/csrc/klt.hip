@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "fundamental.hpp"
 #include "uvo_math.hpp"
 
 namespace uvo {
@@ -287,6 +288,8 @@ struct uvo_klt {
   float *d_prev = nullptr, *d_next = nullptr, *d_err = nullptr;
   uint8_t* d_status = nullptr;
   std::vector<int> slot_w, slot_h, slot_levels;
+  FmScratch fm;          // findFundamentalMat (fundamental.hip)
+  int fm_iters = 0;      // iterations of the last find_fundamental / track_filtered call (the hypothesis tap)
 };
 
 static void klt_geometry(int w, int h, int bx, int by, int max_level, KltGeom& G, int64_t* img_bytes, int64_t* der_shorts) {
@@ -318,6 +321,7 @@ void uvo_klt_destroy(uvo_klt* k) {
   void* ptrs[] = {k->d_img, k->d_der, k->d_in, k->d_pts};
   for (void* p : ptrs)
     if (p) hipFree(p);
+  fm_free(k->fm);
   if (k->h_pts) (void)hipHostFree(k->h_pts);
   if (k->stream) hipStreamDestroy(k->stream);
   delete k;
@@ -342,10 +346,14 @@ int uvo_klt_create(const uvo_klt_cfg* cfg, uvo_klt** out) {
   k->slot_w.assign(cfg->slots, 0), k->slot_h.assign(cfg->slots, 0), k->slot_levels.assign(cfg->slots, 0);
   const size_t S = (size_t)cfg->slots, N = (size_t)cfg->max_points;
   if (hipMalloc((void**)&k->d_img, S * k->img_block) != hipSuccess || hipMalloc((void**)&k->d_der, S * k->der_block * 2) != hipSuccess ||
-      hipMalloc((void**)&k->d_in, (size_t)cfg->max_width * cfg->max_height) != hipSuccess || hipMalloc((void**)&k->d_pts, N * 37 + 64) != hipSuccess ||
-      hipHostMalloc((void**)&k->h_pts, N * 37 + 64, hipHostMallocDefault) != hipSuccess) {
+      hipMalloc((void**)&k->d_in, (size_t)cfg->max_width * cfg->max_height) != hipSuccess || hipMalloc((void**)&k->d_pts, N * 40 + 320) != hipSuccess ||
+      hipHostMalloc((void**)&k->h_pts, N * 40 + 320, hipHostMallocDefault) != hipSuccess) {
     uvo_klt_destroy(k);
     return fail(UVO_E_NOMEM, "KLT scratch allocation failed");
+  }
+  if (const int rc = fm_alloc(k->fm)) {
+    uvo_klt_destroy(k);
+    return rc;
   }
   *out = k;
   return UVO_OK;
@@ -445,9 +453,36 @@ static int check_camera_model(const uvo_camera_model* cam, UndistortCam& C) {
 }
 
 // the LK step, optionally followed on the device by Tracking::undistort_point of both point sets (one upload, one download)
+// findFundamentalMat on the undistorted pairs of a uvo_klt_track_filtered call (thr / conf after fm_fixup)
+struct FmCall {
+  double thr, conf;
+  uint8_t* mask_out;
+  double* F;
+};
+
+static void fm_empty(uvo_klt* k, int n, uint8_t* mask, double* F, uvo_fm_info* info) {
+  if (n > 0) std::memset(mask, 0, (size_t)n);
+  if (F) std::fill(F, F + 9, 0.);
+  if (info) *info = uvo_fm_info{UVO_FM_NONE, 0, 0, 0};
+  k->fm_iters = 0;
+}
+
+// the FmOut + mask that k_fm_replay wrote at byte o_fm of the point block, once downloaded into h_pts
+static int fm_collect(uvo_klt* k, size_t o_fm, int n, uint8_t* mask, double* F, uvo_fm_info* info) {
+  FmOut o;
+  std::memcpy(&o, k->h_pts + o_fm, sizeof o);
+  k->fm_iters = 0;
+  if (o.overflow) return fail(UVO_E_CAPACITY, "findFundamentalMat: one getSubset attempt needed more draws than a window holds");
+  std::memcpy(mask, k->h_pts + o_fm + sizeof(FmOut), (size_t)n);
+  if (F) std::memcpy(F, o.F, sizeof o.F);
+  if (info) std::memcpy(info, &o, sizeof *info);
+  k->fm_iters = o.iterations;
+  return UVO_OK;
+}
+
 static int klt_track_impl(uvo_klt* k, int prev_slot, int next_slot, const float* prev_pts, float* next_pts, int n, int max_level, int max_count,
                           double epsilon, double min_eig_threshold, uint8_t* status, float* err, const uvo_camera_model* cam, float* prev_un,
-                          float* next_un) {
+                          float* next_un, const FmCall* fm = nullptr) {
   if (!k) return fail(UVO_E_BADARG, "null handle");
   if (prev_slot < 0 || prev_slot >= k->cfg.slots || next_slot < 0 || next_slot >= k->cfg.slots || k->slot_levels[prev_slot] == 0 ||
       k->slot_levels[next_slot] == 0)
@@ -498,8 +533,16 @@ static int klt_track_impl(uvo_klt* k, int prev_slot, int next_slot, const float*
     hipLaunchKernelGGL(k_undistort, dim3((n + 255) / 256), dim3(256), 0, s, UC, k->d_next, n, d_un + 2 * N);
   }
   UVO_HIP_CHECK(hipGetLastError());
-  const size_t down = (cam ? o_un + N * 16 : N * 21) - o_next;
-  UVO_HIP_CHECK(hipMemcpyAsync(k->h_pts + o_next, k->d_pts + o_next, down, hipMemcpyDeviceToHost, s));  // next, err, status (, prev_un, next_un)
+  // findFundamentalMat on the undistorted pairs, its FmOut + mask_out behind them (64-byte aligned)
+  const size_t o_fm = (o_un + N * 16 + 63) & ~(size_t)63;
+  if (fm) {
+    const float* d_un = reinterpret_cast<const float*>(k->d_pts + o_un);
+    const int rc = fm_enqueue(s, k->fm, d_un, d_un + 2 * N, n, fm->thr, fm->conf, k->d_status, reinterpret_cast<FmOut*>(k->d_pts + o_fm),
+                              k->d_pts + o_fm + sizeof(FmOut));
+    if (rc) return rc;
+  }
+  const size_t down = (fm ? o_fm + sizeof(FmOut) + N : cam ? o_un + N * 16 : N * 21) - o_next;
+  UVO_HIP_CHECK(hipMemcpyAsync(k->h_pts + o_next, k->d_pts + o_next, down, hipMemcpyDeviceToHost, s));  // next, err, status (, prev_un, next_un (, F, mask))
   UVO_HIP_CHECK(hipStreamSynchronize(s));
   std::memcpy(next_pts, k->h_pts + o_next, N * 8);
   std::memcpy(err, k->h_pts + o_err, N * 4);
@@ -508,6 +551,7 @@ static int klt_track_impl(uvo_klt* k, int prev_slot, int next_slot, const float*
     std::memcpy(prev_un, k->h_pts + o_un, N * 8);
     std::memcpy(next_un, k->h_pts + o_un + N * 8, N * 8);
   }
+  if (fm) return fm_collect(k, o_fm, n, fm->mask_out, fm->F, nullptr);
   return UVO_OK;
 }
 
@@ -525,6 +569,62 @@ int uvo_klt_track_undistorted(uvo_klt* k, int prev_slot, int next_slot, const fl
   if (!cam) return fail(UVO_E_BADARG, "null camera model");
   return klt_track_impl(k, prev_slot, next_slot, prev_pts, next_pts, n, max_level, max_count, epsilon, min_eig_threshold, status, err, cam, prev_un,
                         next_un);
+}
+
+int uvo_klt_track_filtered(uvo_klt* k, int prev_slot, int next_slot, const float* prev_pts, float* next_pts, int n, int max_level, int max_count,
+                           double epsilon, double min_eig_threshold, const uvo_camera_model* cam, uint8_t* status, float* err, float* prev_un,
+                           float* next_un, double thr, double conf, uint8_t* mask_out, double* F) {
+  if (!k) return fail(UVO_E_BADARG, "null handle");
+  if (!cam) return fail(UVO_E_BADARG, "null camera model");
+  if (n < 0 || n > k->cfg.max_points) return fail(UVO_E_BADARG, "point count outside 0..max_points");
+  if (n > 0 && !mask_out) return fail(UVO_E_BADARG, "null pointer");
+  FmCall fc{thr, conf, mask_out, F};
+  if (const int rc = fm_fixup(fc.thr, fc.conf)) return rc;
+  if (n < 10) {  // perform_matching :1037-1041: too few points for RANSAC -- mask all 0, the tracker does not run
+    fm_empty(k, n, mask_out, F, nullptr);
+    return UVO_OK;
+  }
+  return klt_track_impl(k, prev_slot, next_slot, prev_pts, next_pts, n, max_level, max_count, epsilon, min_eig_threshold, status, err, cam, prev_un,
+                        next_un, &fc);
+}
+
+int uvo_klt_find_fundamental(uvo_klt* k, const float* p0, const float* p1, int n, double thr, double conf, uint8_t* mask, double* F,
+                             uvo_fm_info* info) {
+  if (!k) return fail(UVO_E_BADARG, "null handle");
+  if (n < 0 || n > k->cfg.max_points) return fail(UVO_E_BADARG, "point count outside 0..max_points");
+  if (n > 0 && (!p0 || !p1 || !mask)) return fail(UVO_E_BADARG, "null pointer");
+  if (const int rc = fm_fixup(thr, conf)) return rc;
+  if (n < 7) {
+    fm_empty(k, n, mask, F, info);
+    return UVO_OK;
+  }
+  UVO_HIP_CHECK(hipSetDevice(k->cfg.device));
+  hipStream_t s = k->stream;
+  // layout: p0 [n][2] f32 | p1 [n][2] f32 | FmOut (64-byte aligned) | mask [n]
+  const size_t N = (size_t)n, o_fm = (N * 16 + 63) & ~(size_t)63;
+  std::memcpy(k->h_pts, p0, N * 8);
+  std::memcpy(k->h_pts + N * 8, p1, N * 8);
+  UVO_HIP_CHECK(hipMemcpyAsync(k->d_pts, k->h_pts, N * 16, hipMemcpyHostToDevice, s));
+  const float* d_p = reinterpret_cast<const float*>(k->d_pts);
+  const int rc = fm_enqueue(s, k->fm, d_p, d_p + 2 * N, n, thr, conf, nullptr, reinterpret_cast<FmOut*>(k->d_pts + o_fm), k->d_pts + o_fm + sizeof(FmOut));
+  if (rc) return rc;
+  UVO_HIP_CHECK(hipMemcpyAsync(k->h_pts + o_fm, k->d_pts + o_fm, sizeof(FmOut) + N, hipMemcpyDeviceToHost, s));
+  UVO_HIP_CHECK(hipStreamSynchronize(s));
+  return fm_collect(k, o_fm, n, mask, F, info);
+}
+
+int uvo_klt_fm_hypotheses(uvo_klt* k, int32_t* subsets, int32_t* n_models, double* scores, int cap, int* n) {
+  if (!k || !n) return fail(UVO_E_BADARG, "null pointer");
+  if (cap < 0) return fail(UVO_E_BADARG, "negative capacity");
+  const int m = std::min(cap, k->fm_iters);
+  if (m > 0 && (!subsets || !n_models || !scores)) return fail(UVO_E_BADARG, "null pointer");
+  *n = m;
+  if (m == 0) return UVO_OK;
+  UVO_HIP_CHECK(hipSetDevice(k->cfg.device));
+  UVO_HIP_CHECK(hipMemcpy(subsets, k->fm.subsets, (size_t)m * 7 * 4, hipMemcpyDeviceToHost));
+  UVO_HIP_CHECK(hipMemcpy(n_models, k->fm.nmodels, (size_t)m * 4, hipMemcpyDeviceToHost));
+  UVO_HIP_CHECK(hipMemcpy(scores, k->fm.scores, (size_t)m * 3 * 8, hipMemcpyDeviceToHost));
+  return UVO_OK;
 }
 
 int uvo_undistort_points(uvo_klt* k, const uvo_camera_model* cam, const float* pts, int n, float* out) {
