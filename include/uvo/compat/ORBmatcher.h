@@ -24,6 +24,10 @@
  *     device handle (more key points or map points than any call before): the handle that holds the batch is kept for Next until the
  *     next Begin or the destructor, and the other members get a new one.  A Next without a successful Begin returns 0 and sets
  *     last_error().
+ *   CreateNewMapPoints(pKF1, vpKF2, vF12, vNew)                          the loop of src/LocalMapping.cc:1058-1199 in ONE call: per pair the
+ *     matches of SearchForTriangulation AND their triangulation, with pKF1's new map points handed from pair to pair on the device;
+ *     returns per pair (idx1, idx2, x3D) of the accepted matches, in the reference's order -- the map mutation of :1183-1197 is the
+ *     caller's loop over that list.  No cv::SVD, no host work between pairs.
  *   FuseTargets(vpTargetKFs, vpMapPoints, th)                            the loop of src/LocalMapping.cc:1228-1236
  * and the four members nothing in the reference calls (kept so that the class is complete):
  *   WindowSearch(F1, F2, windowSize, vpMapPointMatches2, minOctave, maxOctave)   :409-516
@@ -353,58 +357,71 @@ class UVO_COMPAT_MATCHER_NAME {
    * loop's order, each before the map-point creation that follows it in the reference. */
   template <class KeyFrameT, class Mat33>
   int SearchForTriangulationBegin(KeyFrameT* pKF1, const std::vector<KeyFrameT*>& vpKF2, const std::vector<Mat33>& vF12) {
-    typedef decltype(pKF1->GetKeyPointUn(0)) KeyPointT;
-    static_assert(sizeof(KeyPointT) == sizeof(uvo_keypoint), "keypoint layout must be cv::KeyPoint");
-    const std::vector<KeyPointT> vKeysUn1 = pKF1->GetKeyPointsUn();
-    const auto vpMapPoints1 = pKF1->GetMapPointMatches();
-    const int n1 = (int)vKeysUn1.size(), np = (int)vpKF2.size();
-    int nmax = n1;
-    for (int k = 0; k < np; ++k) nmax = (int)vpKF2[k]->N > nmax ? (int)vpKF2[k]->N : nmax;
-    if (vF12.size() != vpKF2.size() || ensure(nmax, 1) != UVO_OK) return UVO_E_BADARG;
-    FlatFeatureVector f1(pKF1->GetFeatureVector());
-    std::vector<uint8_t> d1((size_t)n1 * 32), has1(n1);
-    for (int i = 0; i < n1; ++i) {
-      auto d = pKF1->GetDescriptor(i);
-      std::memcpy(&d1[(size_t)i * 32], d.ptr(0), 32);
-      has1[i] = vpMapPoints1[i] != NULL;
-    }
-    // per pair: everything the single call marshals (see SearchForTriangulation above), kept alive until the batch call returns
-    std::vector<FlatFeatureVector> f2;
-    std::vector<uvo_feature_vector> c2(np);
-    std::vector<std::vector<KeyPointT> > keys2(np);
-    std::vector<std::vector<uint8_t> > d2(np), has2(np);
-    std::vector<std::vector<float> > sigma2(np);
-    std::vector<uvo_triangulation_pair> pairs(np);
-    f2.reserve(np);
-    for (int k = 0; k < np; ++k) {
-      KeyFrameT* pKF2 = vpKF2[k];
-      keys2[k] = pKF2->GetKeyPointsUn();
-      const auto vpMapPoints2 = pKF2->GetMapPointMatches();
-      const int n2 = (int)keys2[k].size();
-      d2[k].resize((size_t)n2 * 32), has2[k].resize(n2);
-      for (int j = 0; j < n2; ++j) {
-        auto d = pKF2->GetDescriptor(j);
-        std::memcpy(&d2[k][(size_t)j * 32], d.ptr(0), 32);
-        has2[k][j] = vpMapPoints2[j] != NULL;
-      }
-      f2.push_back(FlatFeatureVector(pKF2->GetFeatureVector()));
-      c2[k] = f2.back().c();
-      const int nlev = pKF2->GetScaleLevels();
-      sigma2[k].resize(nlev);
-      for (int l = 0; l < nlev; ++l) sigma2[k][l] = pKF2->GetSigma2(l);
-      uvo_triangulation_pair& P = pairs[k];
-      P.fv2 = &c2[k], P.kp2 = reinterpret_cast<const uvo_keypoint*>(keys2[k].data()), P.n2 = n2, P.desc2 = d2[k].data(), P.has_mp2 = has2[k].data();
-      for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) P.f12[3 * r + c] = vF12[k].template at<float>(r, c);
-      P.sigma2 = sigma2[k].data(), P.nlevels = nlev;
-    }
-    uvo_feature_vector c1 = f1.c();
-    const int rc = uvo_search_for_triangulation_batch(m_, &c1, reinterpret_cast<const uvo_keypoint*>(vKeysUn1.data()), n1, d1.data(), has1.data(), np,
-                                                      pairs.data());
+    TriLoop<KeyFrameT> L;
+    if (vF12.size() != vpKF2.size() || ensure(L.nmax(pKF1, vpKF2), 1) != UVO_OK) return UVO_E_BADARG;
+    L.marshal(pKF1, vpKF2, vF12);
+    uvo_feature_vector c1 = L.f1.c();
+    const int rc = uvo_search_for_triangulation_batch(m_, &c1, reinterpret_cast<const uvo_keypoint*>(L.keys1.data()), L.n1, L.d1.data(), L.has1.data(),
+                                                      (int)vpKF2.size(), L.pairs.data());
     if (tri_ != m_) uvo_matcher_destroy(tri_);  // a new batch replaces the old one, on whichever handle it lives
     tri_ = rc == UVO_OK ? m_ : nullptr;
     if (rc != UVO_OK) err_ = uvo_last_error();
     return rc;
+  }
+  /* One accepted match of the loop body of LocalMapping::CreateNewMapPoints: what :1183-1189 needs (`new MapPoint(x3D, ...)`,
+   * AddObservation(pKF2, idx2), AddObservation(mpCurrentKeyFrame, idx1)). */
+  struct NewMapPoint {
+    size_t idx1, idx2;
+    float x3D[3];
+  };
+  /* The whole loop of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:1058-1199) as one call.  vpKF2 / vF12: the neighbours that
+   * passed the baseline test of :1066-1072 and their ComputeF12 (:1074).  vNew[k]: the accepted matches of neighbour k in the order
+   * the reference's inner loop creates their map points (ascending idx1); pKF1's features that got a point in pair k are no queries of
+   * pair k + 1, exactly as after AddMapPoint (:1188).  The caller then runs :1183-1197 over vNew.  Returns the number of new points, or
+   * a negative UVO_E_* code. */
+  template <class KeyFrameT, class Mat33>
+  int CreateNewMapPoints(KeyFrameT* pKF1, const std::vector<KeyFrameT*>& vpKF2, const std::vector<Mat33>& vF12,
+                         std::vector<std::vector<NewMapPoint> >& vNew) {
+    vNew.assign(vpKF2.size(), std::vector<NewMapPoint>());
+    TriLoop<KeyFrameT> L;
+    if (vF12.size() != vpKF2.size() || ensure(L.nmax(pKF1, vpKF2), 1) != UVO_OK) return UVO_E_BADARG;
+    L.marshal(pKF1, vpKF2, vF12);
+    const int np = (int)vpKF2.size(), n1 = L.n1;
+    if (np == 0 || n1 == 0) return 0;
+    TriCamera cam1(pKF1);
+    std::vector<TriCamera> keep;
+    std::vector<uvo_triangulation_camera> cams2(np);
+    keep.reserve(np);
+    for (int k = 0; k < np; ++k) {
+      keep.push_back(TriCamera(vpKF2[k]));
+      cams2[k] = keep.back().c();
+    }
+    const uvo_triangulation_camera c1cam = cam1.c();
+    const float ratioFactor = 1.5f * cam1.sf[cam1.sf.size() > 1 ? 1 : 0];  // 1.5f * GetScaleFactor(), :1055 (GetScaleFactor(nLevel = 1))
+    std::vector<int32_t> nm(np), na(np), idx1((size_t)np * n1), idx2((size_t)np * n1), verdict((size_t)np * n1);
+    std::vector<float> x3d((size_t)np * n1 * 3);
+    uvo_new_map_points out;
+    out.n_matches = nm.data(), out.n_accepted = na.data(), out.idx1 = idx1.data(), out.idx2 = idx2.data(), out.verdict = verdict.data();
+    out.x3d = x3d.data(), out.has_mp1_out = nullptr;
+    uvo_feature_vector c1 = L.f1.c();
+    const int rc = uvo_create_new_map_points(m_, &c1, reinterpret_cast<const uvo_keypoint*>(L.keys1.data()), n1, L.d1.data(), L.has1.data(), np,
+                                             L.pairs.data(), &c1cam, cams2.data(), ratioFactor, mbCheckOrientation ? 1 : 0, &out);
+    if (rc != UVO_OK) {
+      err_ = uvo_last_error();
+      return rc;
+    }
+    int created = 0;
+    for (int k = 0; k < np; ++k)
+      for (int j = 0; j < nm[k]; ++j) {
+        const size_t e = (size_t)k * n1 + j;
+        if (verdict[e] != UVO_TRI_ACCEPTED) continue;
+        NewMapPoint P;
+        P.idx1 = (size_t)idx1[e], P.idx2 = (size_t)idx2[e];
+        for (int c = 0; c < 3; ++c) P.x3D[c] = x3d[e * 3 + c];
+        vNew[k].push_back(P);
+        ++created;
+      }
+    return created;
   }
   template <class KeyFrameT, class KeyPointT>
   int SearchForTriangulationNext(KeyFrameT* pKF1, KeyFrameT* pKF2, int k, std::vector<KeyPointT>& vMatchedKeys1, std::vector<KeyPointT>& vMatchedKeys2,
@@ -918,6 +935,7 @@ class UVO_COMPAT_MATCHER_NAME {
   struct FlatFeatureVector {
     std::vector<uint32_t> node;
     std::vector<int32_t> start, feat;
+    FlatFeatureVector() {}
     template <class FeatVec>
     explicit FlatFeatureVector(const FeatVec& fv) {
       start.push_back(0);
@@ -930,6 +948,91 @@ class UVO_COMPAT_MATCHER_NAME {
     uvo_feature_vector c() const {
       uvo_feature_vector v;
       v.node = node.data(), v.start = start.data(), v.feat = feat.data(), v.n_nodes = (int32_t)node.size();
+      return v;
+    }
+  };
+  /* everything the loop of CreateNewMapPoints marshals once: key frame 1, and per neighbour what the single SearchForTriangulation call
+   * marshals; kept alive until the library call returns */
+  template <class KeyFrameT>
+  struct TriLoop {
+    typedef decltype(std::declval<KeyFrameT&>().GetKeyPointUn(0)) KeyPointT;
+    static_assert(sizeof(KeyPointT) == sizeof(uvo_keypoint), "keypoint layout must be cv::KeyPoint");
+    int n1 = 0;
+    std::vector<KeyPointT> keys1;
+    FlatFeatureVector f1;
+    std::vector<uint8_t> d1, has1;
+    std::vector<FlatFeatureVector> f2;
+    std::vector<uvo_feature_vector> c2;
+    std::vector<std::vector<KeyPointT> > keys2;
+    std::vector<std::vector<uint8_t> > d2, has2;
+    std::vector<std::vector<float> > sigma2;
+    std::vector<uvo_triangulation_pair> pairs;
+    static int nmax(KeyFrameT* pKF1, const std::vector<KeyFrameT*>& vpKF2) {
+      int n = (int)pKF1->GetKeyPointsUn().size();
+      for (size_t k = 0; k < vpKF2.size(); ++k) n = (int)vpKF2[k]->N > n ? (int)vpKF2[k]->N : n;
+      return n;
+    }
+    template <class Mat33>
+    void marshal(KeyFrameT* pKF1, const std::vector<KeyFrameT*>& vpKF2, const std::vector<Mat33>& vF12) {
+      keys1 = pKF1->GetKeyPointsUn();
+      const auto vpMapPoints1 = pKF1->GetMapPointMatches();
+      n1 = (int)keys1.size();
+      const int np = (int)vpKF2.size();
+      f1 = FlatFeatureVector(pKF1->GetFeatureVector());
+      d1.resize((size_t)n1 * 32), has1.resize(n1);
+      for (int i = 0; i < n1; ++i) {
+        auto d = pKF1->GetDescriptor(i);
+        std::memcpy(&d1[(size_t)i * 32], d.ptr(0), 32);
+        has1[i] = vpMapPoints1[i] != NULL;
+      }
+      c2.resize(np), keys2.resize(np), d2.resize(np), has2.resize(np), sigma2.resize(np), pairs.resize(np);
+      f2.reserve(np);
+      for (int k = 0; k < np; ++k) {
+        KeyFrameT* pKF2 = vpKF2[k];
+        keys2[k] = pKF2->GetKeyPointsUn();
+        const auto vpMapPoints2 = pKF2->GetMapPointMatches();
+        const int n2 = (int)keys2[k].size();
+        d2[k].resize((size_t)n2 * 32), has2[k].resize(n2);
+        for (int j = 0; j < n2; ++j) {
+          auto d = pKF2->GetDescriptor(j);
+          std::memcpy(&d2[k][(size_t)j * 32], d.ptr(0), 32);
+          has2[k][j] = vpMapPoints2[j] != NULL;
+        }
+        f2.push_back(FlatFeatureVector(pKF2->GetFeatureVector()));
+        c2[k] = f2.back().c();
+        const int nlev = pKF2->GetScaleLevels();
+        sigma2[k].resize(nlev);
+        for (int l = 0; l < nlev; ++l) sigma2[k][l] = pKF2->GetSigma2(l);
+        uvo_triangulation_pair& P = pairs[k];
+        P.fv2 = &c2[k], P.kp2 = reinterpret_cast<const uvo_keypoint*>(keys2[k].data()), P.n2 = n2, P.desc2 = d2[k].data(), P.has_mp2 = has2[k].data();
+        for (int r = 0; r < 3; ++r)
+          for (int c = 0; c < 3; ++c) P.f12[3 * r + c] = vF12[k].template at<float>(r, c);
+        P.sigma2 = sigma2[k].data(), P.nlevels = nlev;
+      }
+    }
+  };
+  /* a key frame as the triangulation reads it (uvo_triangulation_camera), level tables kept alive */
+  struct TriCamera {
+    uvo_triangulation_camera cam;
+    std::vector<float> sf, sigma2;
+    template <class KeyFrameT>
+    explicit TriCamera(KeyFrameT* pKF) {
+      auto Rcw = pKF->GetRotation();
+      auto tcw = pKF->GetTranslation();
+      auto Ow = pKF->GetCameraCenter();
+      for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) cam.rcw[3 * r + c] = Rcw.template at<float>(r, c);
+        cam.tcw[r] = tcw.template at<float>(r);
+        cam.ow[r] = Ow.template at<float>(r);
+      }
+      cam.fx = pKF->fx, cam.fy = pKF->fy, cam.cx = pKF->cx, cam.cy = pKF->cy;
+      sf = pKF->GetScaleFactors();
+      sigma2.resize(sf.size());
+      for (size_t l = 0; l < sf.size(); ++l) sigma2[l] = pKF->GetSigma2((int)l);
+    }
+    uvo_triangulation_camera c() const {
+      uvo_triangulation_camera v = cam;
+      v.scale_factors = sf.data(), v.sigma2 = sigma2.data(), v.nlevels = (int32_t)sf.size();
       return v;
     }
   };

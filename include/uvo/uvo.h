@@ -575,6 +575,70 @@ int uvo_search_for_triangulation_batch(uvo_matcher* m, const uvo_feature_vector*
 int uvo_search_for_triangulation_next(uvo_matcher* m, int pair, const uint8_t* has_mp1_now, int check_orientation, int32_t* match12,
                                       int* n_matches);
 /*
+ * The second half of LocalMapping::CreateNewMapPoints: the triangulation of a pair's matches (src/LocalMapping.cc:1096-1180; the same
+ * linear method as Initializer::Triangulate, src/Initializer.cc:726-745) -- parallax between the rays, 4 x 4 linear triangulation by
+ * SVD, depth signs, the two reprojection tests, scale consistency -- one device lane per match, in the reference's operation order
+ * and types (fp32, double where the reference's expression is double).  Verdicts name the `continue` a match left the loop body at.
+ */
+enum {
+  UVO_TRI_ACCEPTED = 0,  /* :1182 "Triangulation is succesfull" */
+  UVO_TRI_PARALLAX = 1,  /* :1112 cosParallaxRays < 0 || cosParallaxRays > 0.9998 */
+  UVO_TRI_W_ZERO = 2,    /* :1127 homogeneous coordinate == 0 */
+  UVO_TRI_BEHIND_1 = 3,  /* :1136 z1 <= 0 */
+  UVO_TRI_BEHIND_2 = 4,  /* :1140 z2 <= 0 */
+  UVO_TRI_REPROJ_1 = 5,  /* :1152 reprojection error in key frame 1 > 5.991 sigma2 */
+  UVO_TRI_REPROJ_2 = 6,  /* :1164 reprojection error in key frame 2 */
+  UVO_TRI_ZERO_DIST = 7, /* :1174 dist1 == 0 || dist2 == 0 */
+  UVO_TRI_SCALE = 8      /* :1179 distance ratio against the octave ratio */
+};
+typedef struct uvo_triangulation_camera {
+  float rcw[9];               /* GetRotation(), row-major */
+  float tcw[3];               /* GetTranslation() */
+  float ow[3];                /* GetCameraCenter(): passed in, not derived, so that it is the key frame's own Ow bit for bit */
+  float fx, fy, cx, cy;
+  const float* scale_factors; /* [nlevels] GetScaleFactor(level) */
+  const float* sigma2;        /* [nlevels] GetSigma2(level) */
+  int32_t nlevels;            /* 1 .. 64; every key point's octave must lie inside */
+} uvo_triangulation_camera;
+/*
+ * The core alone, for a caller-given list of n matched undistorted key points (kp1[j] in key frame 1 <-> kp2[j] in key frame 2; x, y,
+ * octave are read).  ratio_factor = 1.5f * mpCurrentKeyFrame->GetScaleFactor() (:1055).  Host buffers.
+ *   verdict[n] : UVO_TRI_*;  x3d[n][3] : the point wherever the verdict is ACCEPTED or >= BEHIND_1 (it exists from :1131 on), zeros else
+ * Tolerance contract: the fp32 SVD is OpenCV 3.4's one-sided Jacobi restated, not OpenCV's binary; x3d agrees
+ * with a float64 evaluation within a stated relative bound and verdicts are exact except where a test lies within a stated margin of
+ * its threshold.
+ */
+int uvo_triangulate_matches(uvo_matcher* m, const uvo_triangulation_camera* cam1, const uvo_triangulation_camera* cam2, float ratio_factor,
+                            const uvo_keypoint* kp1, const uvo_keypoint* kp2, int n, int32_t* verdict, float* x3d);
+/*
+ * The whole loop of src/LocalMapping.cc:1058-1199 in one call: the arguments of uvo_search_for_triangulation_batch, plus the cameras.
+ * For each pair, in order, on the device: the acceptance loop of SearchForTriangulation (src/ORBmatcher.cc:886-984) with key frame 1's
+ * map points as they are BY THEN, the triangulation of that pair's matches, and has_mp1 = 1 for the accepted ones -- so pair k + 1
+ * sees the map points pair k created, with no host visit in between: one upload, one launch chain, one host wait.  The short-baseline
+ * skip (:1066-1072) and ComputeF12 stay with the caller (skipped pairs are left out; f12 travels in uvo_triangulation_pair); the map
+ * mutation (new MapPoint, AddObservation, ...) stays on the host, done after the call in the order of the output, the reference's order.
+ *   cams2[n_pairs]           : camera of key frame 2 of every pair; cam1 / ratio_factor as in uvo_triangulate_matches
+ * Outputs, every array [n_pairs][n1] (pair p's entries start at element p * n1; a pair has at most n1 matches):
+ *   n_matches[n_pairs]       : matches of pair p = vMatchedIndices.size() at that point of the reference's loop
+ *   n_accepted[n_pairs]      : how many of them were accepted
+ *   idx1, idx2               : the matches, ascending idx1 -- exactly vMatchedIndices
+ *   verdict, x3d ([..][3])   : per match, as uvo_triangulate_matches
+ *   has_mp1_out[n1]          : has_mp1 after the loop (may be NULL)
+ * A batch that uvo_search_for_triangulation_batch left in the handle is not touched (it lives on the host).
+ */
+typedef struct uvo_new_map_points {
+  int32_t* n_matches;
+  int32_t* n_accepted;
+  int32_t* idx1;
+  int32_t* idx2;
+  int32_t* verdict;
+  float* x3d;
+  uint8_t* has_mp1_out;
+} uvo_new_map_points;
+int uvo_create_new_map_points(uvo_matcher* m, const uvo_feature_vector* fv1, const uvo_keypoint* kp1, int n1, const uint8_t* desc1,
+                              const uint8_t* has_mp1, int n_pairs, const uvo_triangulation_pair* pairs, const uvo_triangulation_camera* cam1,
+                              const uvo_triangulation_camera* cams2, float ratio_factor, int check_orientation, const uvo_new_map_points* out);
+/*
  * LocalMapping::SearchInNeighbors (src/LocalMapping.cc:1228-1236) calls Fuse(pKFi, vpMapPointMatches) for every target key frame.  The
  * search core of Fuse has no exclusivity among the map points, so the projection tests (:1037-1075, with each target's own pose) and the
  * best key point (:1077-1101) of EVERY (target, map point) are computed in one pass: the map points are uploaded once, each target adds

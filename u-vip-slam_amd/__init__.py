@@ -42,7 +42,7 @@ ABI_SYMBOLS = [
     "uvo_grider_fast", "uvo_clahe", "uvo_clahe_batch_device", "uvo_extractor_read_plane", "uvo_extractor_read_candidates", "uvo_extractor_profile", "uvo_extractor_profile_only", "uvo_extractor_kernel_times",
     "uvo_matcher_create", "uvo_matcher_destroy", "uvo_matcher_synchronize", "uvo_hamming_knn2", "uvo_hamming_knn2_batch_device",
     "uvo_hamming_matrix", "uvo_distinctive_descriptors", "uvo_search_by_projection", "uvo_match_windows", "uvo_match_groups",
-    "uvo_search_by_projection_kf", "uvo_search_by_bow", "uvo_search_for_triangulation", "uvo_search_for_triangulation_batch", "uvo_search_for_triangulation_next", "uvo_fuse", "uvo_fuse_batch", "uvo_project_points", "uvo_search_points_in_frustum", "uvo_sim3_decompose", "uvo_sim3_relative", "uvo_project_sim3", "uvo_search_by_projection_sim3", "uvo_search_by_sim3", "uvo_haloc_hash", "uvo_klt_create", "uvo_klt_destroy", "uvo_klt_build_pyramid", "uvo_klt_build_pyramid_from_extractor", "uvo_klt_read_level", "uvo_klt_track", "uvo_undistort_points", "uvo_klt_track_undistorted", "uvo_klt_find_fundamental", "uvo_klt_track_filtered", "uvo_klt_fm_hypotheses", "uvo_vocabulary_create", "uvo_vocabulary_destroy", "uvo_bow_transform", "uvo_matcher_wait_extractor", "uvo_extractor_wait_matcher", "uvo_matcher_attach_extractor", "uvo_matcher_profile",
+    "uvo_search_by_projection_kf", "uvo_search_by_bow", "uvo_search_for_triangulation", "uvo_search_for_triangulation_batch", "uvo_search_for_triangulation_next", "uvo_triangulate_matches", "uvo_create_new_map_points", "uvo_fuse", "uvo_fuse_batch", "uvo_project_points", "uvo_search_points_in_frustum", "uvo_sim3_decompose", "uvo_sim3_relative", "uvo_project_sim3", "uvo_search_by_projection_sim3", "uvo_search_by_sim3", "uvo_haloc_hash", "uvo_klt_create", "uvo_klt_destroy", "uvo_klt_build_pyramid", "uvo_klt_build_pyramid_from_extractor", "uvo_klt_read_level", "uvo_klt_track", "uvo_undistort_points", "uvo_klt_track_undistorted", "uvo_klt_find_fundamental", "uvo_klt_track_filtered", "uvo_klt_fm_hypotheses", "uvo_vocabulary_create", "uvo_vocabulary_destroy", "uvo_bow_transform", "uvo_matcher_wait_extractor", "uvo_extractor_wait_matcher", "uvo_matcher_attach_extractor", "uvo_matcher_profile",
     "uvo_matcher_kernel_times", "uvo_last_error", "uvo_device_info",
 ]
 
@@ -89,6 +89,37 @@ class TriangulationPairC(ctypes.Structure):
     """uvo_triangulation_pair."""
     _fields_ = [("fv2", ctypes.c_void_p), ("kp2", ctypes.c_void_p), ("n2", ctypes.c_int32), ("desc2", ctypes.c_void_p), ("has_mp2", ctypes.c_void_p),
                 ("f12", ctypes.c_float * 9), ("sigma2", ctypes.c_void_p), ("nlevels", ctypes.c_int32)]
+
+
+class TriangulationCameraC(ctypes.Structure):
+    """uvo_triangulation_camera."""
+    _fields_ = [("rcw", ctypes.c_float * 9), ("tcw", ctypes.c_float * 3), ("ow", ctypes.c_float * 3), ("fx", ctypes.c_float), ("fy", ctypes.c_float),
+                ("cx", ctypes.c_float), ("cy", ctypes.c_float), ("scale_factors", ctypes.c_void_p), ("sigma2", ctypes.c_void_p), ("nlevels", ctypes.c_int32)]
+
+
+class NewMapPointsC(ctypes.Structure):
+    """uvo_new_map_points."""
+    _fields_ = [("n_matches", ctypes.c_void_p), ("n_accepted", ctypes.c_void_p), ("idx1", ctypes.c_void_p), ("idx2", ctypes.c_void_p),
+                ("verdict", ctypes.c_void_p), ("x3d", ctypes.c_void_p), ("has_mp1_out", ctypes.c_void_p)]
+
+
+TRI_ACCEPTED, TRI_PARALLAX, TRI_W_ZERO, TRI_BEHIND_1, TRI_BEHIND_2, TRI_REPROJ_1, TRI_REPROJ_2, TRI_ZERO_DIST, TRI_SCALE = range(9)
+
+
+class TriangulationCamera:
+    """A key frame as the triangulation reads it (uvo_triangulation_camera): Rcw, tcw, Ow = GetCameraCenter(), intrinsics and the level
+    tables GetScaleFactor(level) / GetSigma2(level).  Keeps the tables alive for the C struct."""
+
+    def __init__(self, rcw, tcw, ow, fx, fy, cx, cy, scale_factors, sigma2):
+        self.sf = np.ascontiguousarray(scale_factors, np.float32)
+        self.sigma2 = np.ascontiguousarray(sigma2, np.float32)
+        assert len(self.sf) == len(self.sigma2)
+        c = self.c = TriangulationCameraC()
+        c.rcw[:] = [float(x) for x in np.asarray(rcw, np.float32).reshape(9)]
+        c.tcw[:] = [float(x) for x in np.asarray(tcw, np.float32).reshape(3)]
+        c.ow[:] = [float(x) for x in np.asarray(ow, np.float32).reshape(3)]
+        c.fx, c.fy, c.cx, c.cy = float(fx), float(fy), float(cx), float(cy)
+        c.scale_factors, c.sigma2, c.nlevels = self.sf.ctypes.data, self.sigma2.ctypes.data, len(self.sf)
 
 
 class FuseTargetC(ctypes.Structure):
@@ -230,6 +261,8 @@ def _load():
     lib.uvo_fuse.argtypes = [vp, vp, ci, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, ci, cf, vp, vp]
     lib.uvo_search_for_triangulation_batch.argtypes = [vp, vp, vp, ci, vp, vp, ci, vp]
     lib.uvo_search_for_triangulation_next.argtypes = [vp, ci, vp, ci, vp, vp]
+    lib.uvo_triangulate_matches.argtypes = [vp, vp, vp, cf, vp, vp, ci, vp, vp]
+    lib.uvo_create_new_map_points.argtypes = [vp, vp, vp, ci, vp, vp, ci, vp, vp, vp, cf, ci, vp]
     lib.uvo_fuse_batch.argtypes = [vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, cf, vp, vp]
     lib.uvo_search_points_in_frustum.argtypes = [vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, ci, cf, cf, cf, cf, vp, vp, vp, vp, vp, vp, vp]
     lib.uvo_sim3_decompose.argtypes = [vp, ci, vp]
@@ -860,6 +893,53 @@ class ORBmatcher:
         if rc:
             raise UvoError(rc, "uvo_search_for_triangulation_next")
         return match, nm.value
+
+    def TriangulateMatches(self, cam1, cam2, ratio_factor, kp1, kp2):
+        """uvo_triangulate_matches: the triangulation of src/LocalMapping.cc:1096-1180 for a list of matched undistorted key points
+        (kp1[j] <-> kp2[j]).  cam1 / cam2: TriangulationCamera.  Returns (verdict[n] of TRI_*, x3d[n][3])."""
+        kp1, kp2 = np.ascontiguousarray(kp1, KEYPOINT_DTYPE), np.ascontiguousarray(kp2, KEYPOINT_DTYPE)
+        assert len(kp1) == len(kp2)
+        n = len(kp1)
+        verdict, x3d = np.full(n, -1, np.int32), np.zeros((n, 3), np.float32)
+        rc = lib.uvo_triangulate_matches(self._h, ctypes.byref(cam1.c), ctypes.byref(cam2.c), float(ratio_factor), _ptr(kp1), _ptr(kp2), n, _ptr(verdict),
+                                         _ptr(x3d))
+        if rc:
+            raise UvoError(rc, "uvo_triangulate_matches")
+        return verdict, x3d
+
+    def CreateNewMapPoints(self, fv1, kp1, desc1, has_mp1, pairs, cam1, cams2, ratio_factor):
+        """uvo_create_new_map_points: the loop of src/LocalMapping.cc:1058-1199 in one call -- per pair, in order, on the device: the
+        acceptance loop of SearchForTriangulation with key frame 1's map points as they are by then, the triangulation of the pair's
+        matches, has_mp1 = 1 for the accepted ones.  pairs as in SearchForTriangulationBatch; cam1 and cams2[k]: TriangulationCamera.
+        Returns (per_pair, has_mp1_after): per_pair[k] = dict(idx1, idx2, verdict, x3d, n_accepted), the matches in ascending idx1."""
+        kp1 = np.ascontiguousarray(kp1, KEYPOINT_DTYPE)
+        d1, h1 = np.ascontiguousarray(desc1, np.uint8), np.ascontiguousarray(has_mp1, np.uint8)
+        keep = [kp1, d1, h1, fv1]
+        assert len(cams2) == len(pairs)
+        arr = (TriangulationPairC * max(len(pairs), 1))()
+        cams = (TriangulationCameraC * max(len(pairs), 1))()
+        for k, (fv2, kp2, desc2, has_mp2, F12, sigma2) in enumerate(pairs):
+            kp2 = np.ascontiguousarray(kp2, KEYPOINT_DTYPE)
+            d2, h2 = np.ascontiguousarray(desc2, np.uint8), np.ascontiguousarray(has_mp2, np.uint8)
+            s2 = np.ascontiguousarray(sigma2, np.float32)
+            keep += [fv2, kp2, d2, h2, s2]
+            arr[k].fv2, arr[k].kp2, arr[k].n2, arr[k].desc2, arr[k].has_mp2 = ctypes.addressof(fv2.c), _ptr(kp2), len(kp2), _ptr(d2), _ptr(h2)
+            arr[k].f12[:] = [float(x) for x in np.asarray(F12, np.float32).reshape(9)]
+            arr[k].sigma2, arr[k].nlevels = _ptr(s2), len(s2)
+            cams[k] = cams2[k].c
+        P, n1 = len(pairs), len(kp1)
+        nm, na = np.zeros(max(P, 1), np.int32), np.zeros(max(P, 1), np.int32)
+        idx1, idx2 = np.full((max(P, 1), max(n1, 1)), -1, np.int32), np.full((max(P, 1), max(n1, 1)), -1, np.int32)
+        verdict, x3d = np.full((max(P, 1), max(n1, 1)), -1, np.int32), np.zeros((max(P, 1), max(n1, 1), 3), np.float32)
+        h_out = np.zeros(max(n1, 1), np.uint8)
+        out = NewMapPointsC(_ptr(nm), _ptr(na), _ptr(idx1), _ptr(idx2), _ptr(verdict), _ptr(x3d), _ptr(h_out))
+        rc = lib.uvo_create_new_map_points(self._h, ctypes.byref(fv1.c), _ptr(kp1), n1, _ptr(d1), _ptr(h1), P, arr, ctypes.byref(cam1.c), cams,
+                                           float(ratio_factor), 1 if self.mbCheckOrientation else 0, ctypes.byref(out))
+        if rc:
+            raise UvoError(rc, "uvo_create_new_map_points")
+        per_pair = [dict(idx1=idx1[k, :nm[k]].copy(), idx2=idx2[k, :nm[k]].copy(), verdict=verdict[k, :nm[k]].copy(), x3d=x3d[k, :nm[k]].copy(),
+                         n_accepted=int(na[k])) for k in range(P)]
+        return per_pair, h_out[:n1].copy()
 
     def FuseBatch(self, targets, xyz, normal, min_distance, max_distance, usable, mp_desc, th=3.0):
         """uvo_fuse_batch: projection tests + search core of Fuse (:1037-1101) for every (target key frame, map point) in one pass.

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "matcher_priv.hpp"
+#include "triangulate.hpp"
 
 namespace uvo {
 // what uvo_search_for_triangulation_batch leaves in the handle for the _next calls
@@ -61,35 +62,48 @@ void three_maxima(const int* hist, int L, int& ind1, int& ind2, int& ind3) {
     ind3 = -1;
   }
 }
-}  // namespace
 
-extern "C" {
+struct Drain {  // waits for the stream on every way out of a block whose host vectors an enqueued copy still reads
+  hipStream_t s;
+  bool armed;
+  ~Drain() {
+    if (armed) (void)hipStreamSynchronize(s);
+  }
+};
 
-int uvo_search_for_triangulation_batch(uvo_matcher* m, const uvo_feature_vector* fv1, const uvo_keypoint* kp1, int n1, const uint8_t* desc1,
-                                       const uint8_t* has_mp1, int n_pairs, const uvo_triangulation_pair* pairs) {
-  if (!m) return fail(UVO_E_BADARG, "null handle");
-  tri_batch_free(m->tri_batch);
-  m->tri_batch = nullptr;
+// Host staging of the candidate lists of every pair of a CreateNewMapPoints loop and, after tri_stage_launch, their device copies.
+struct TriStage {
+  std::vector<int32_t> cidx, q_pair, pair_base, tlevel, il;
+  std::vector<float> tx, ty, tangle, f12, sigma, fl;
+  std::vector<uint8_t> qdesc, tdesc;
+  int sig_stride = 1, nq = 0, total = 0;
+  size_t nt = 0;
+  bool with_angles = false;  // also stage key frame 2's key point angles (the device-side rotation filter reads them)
+  uint8_t *d_qdesc = nullptr, *d_tdesc = nullptr;
+  int32_t *d_tlevel = nullptr, *d_start = nullptr, *d_cidx = nullptr, *d_il = nullptr;
+  float* d_fl = nullptr;
+  uint32_t* d_cand = nullptr;
+  const float *d_tx = nullptr, *d_ty = nullptr, *d_tangle = nullptr;
+};
+
+// argument checks + the query / candidate lists of all pairs in the reference's visiting order (host work only)
+int tri_stage_build(const uvo_feature_vector* fv1, const uvo_keypoint* kp1, int n1, const uint8_t* desc1, const uint8_t* has_mp1, int n_pairs,
+                    const uvo_triangulation_pair* pairs, bool with_angles, TriBatch* tb, TriStage& S) {
   if (n1 < 0 || n_pairs < 0 || n_pairs > 4096) return fail(UVO_E_BADARG, "bad sizes");
   if (n_pairs > 0 && !pairs) return fail(UVO_E_BADARG, "null pointer");
   if (n1 > 0 && (!kp1 || !desc1 || !has_mp1)) return fail(UVO_E_BADARG, "null pointer");
   RC(check_fv(fv1, n1));
-  TriBatch* tb = new TriBatch();
-  struct Guard {
-    TriBatch* t;
-    ~Guard() { delete t; }
-  } guard{tb};
+  S.with_angles = with_angles;
   tb->n1 = n1, tb->n_pairs = n_pairs;
   tb->has_mp1.assign(has_mp1, has_mp1 + n1);
   tb->angle1.resize(n1);
   for (int i = 0; i < n1; ++i) tb->angle1[i] = kp1[i].angle;
   tb->pairs.resize(n_pairs);
   tb->start.assign(1, 0);
-  std::vector<int32_t> cidx, q_pair, pair_base(std::max(n_pairs, 1), 0), tlevel;
-  std::vector<float> tx, ty, f12((size_t)std::max(n_pairs, 1) * 9, 0.f);
-  int sig_stride = 1;
-  for (int p = 0; p < n_pairs; ++p) sig_stride = std::max(sig_stride, pairs[p].nlevels);
-  std::vector<float> sigma((size_t)std::max(n_pairs, 1) * sig_stride, 0.f);
+  S.pair_base.assign(std::max(n_pairs, 1), 0);
+  S.f12.assign((size_t)std::max(n_pairs, 1) * 9, 0.f);
+  for (int p = 0; p < n_pairs; ++p) S.sig_stride = std::max(S.sig_stride, pairs[p].nlevels);
+  S.sigma.assign((size_t)std::max(n_pairs, 1) * S.sig_stride, 0.f);
   size_t nt = 0;
   for (int p = 0; p < n_pairs; ++p) {
     const uvo_triangulation_pair& P = pairs[p];
@@ -101,13 +115,14 @@ int uvo_search_for_triangulation_batch(uvo_matcher* m, const uvo_feature_vector*
     TriBatch::Pair& Q = tb->pairs[p];
     Q.n2 = P.n2, Q.q_begin = (int)tb->q_idx1.size();
     Q.angle2.resize(P.n2);
-    pair_base[p] = (int32_t)nt;
+    S.pair_base[p] = (int32_t)nt;
     for (int k = 0; k < P.n2; ++k) {
       Q.angle2[k] = P.kp2[k].angle;
-      tx.push_back(P.kp2[k].x), ty.push_back(P.kp2[k].y), tlevel.push_back(P.kp2[k].octave);
+      S.tx.push_back(P.kp2[k].x), S.ty.push_back(P.kp2[k].y), S.tlevel.push_back(P.kp2[k].octave);
+      if (with_angles) S.tangle.push_back(P.kp2[k].angle);
     }
-    memcpy(&f12[(size_t)p * 9], P.f12, 9 * sizeof(float));
-    memcpy(&sigma[(size_t)p * sig_stride], P.sigma2, (size_t)P.nlevels * sizeof(float));
+    memcpy(&S.f12[(size_t)p * 9], P.f12, 9 * sizeof(float));
+    memcpy(&S.sigma[(size_t)p * S.sig_stride], P.sigma2, (size_t)P.nlevels * sizeof(float));
     // queries in the reference's visiting order: shared nodes ascending, features of key frame 1 in node order (:886-892); candidates =
     // the node's features of key frame 2 without a map point (`|| pMP2`, :903-905), in node order
     int a = 0, b = 0;
@@ -117,12 +132,12 @@ int uvo_search_for_triangulation_batch(uvo_matcher* m, const uvo_feature_vector*
           const int idx1 = fv1->feat[e];
           if (has_mp1[idx1]) continue;
           tb->q_idx1.push_back(idx1);
-          q_pair.push_back(p);
+          S.q_pair.push_back(p);
           for (int e2 = P.fv2->start[b]; e2 < P.fv2->start[b + 1]; ++e2) {
             const int idx2 = P.fv2->feat[e2];
-            if (!P.has_mp2[idx2]) cidx.push_back((int32_t)nt + idx2);
+            if (!P.has_mp2[idx2]) S.cidx.push_back((int32_t)nt + idx2);
           }
-          tb->start.push_back((int32_t)cidx.size());
+          tb->start.push_back((int32_t)S.cidx.size());
         }
         ++a, ++b;
       } else if (fv1->node[a] < P.fv2->node[b]) {
@@ -134,53 +149,95 @@ int uvo_search_for_triangulation_batch(uvo_matcher* m, const uvo_feature_vector*
     Q.q_end = (int)tb->q_idx1.size();
     nt += (size_t)P.n2;
   }
-  const int nq = (int)tb->q_idx1.size(), total = (int)cidx.size();
-  tb->cand.assign((size_t)total, 0u);
-  if (total > 0) {
+  S.nt = nt;
+  S.nq = (int)tb->q_idx1.size(), S.total = (int)S.cidx.size();
+  tb->cand.assign((size_t)S.total, 0u);
+  return UVO_OK;
+}
+
+// uploads + the distances and epipolar tests of every pair in one launch; the packed candidates stay in S.d_cand.  S.total > 0.
+int tri_stage_launch(uvo_matcher* m, const uvo_keypoint* kp1, const uint8_t* desc1, int n_pairs, const uvo_triangulation_pair* pairs,
+                     const TriBatch* tb, TriStage& S) {
+  const int nq = S.nq;
+  const size_t nt = S.nt;
+  S.qdesc.resize((size_t)nq * 32), S.tdesc.resize(nt * 32);
+  std::vector<float> qx(nq), qy(nq);
+  for (int i = 0; i < nq; ++i) {
+    memcpy(&S.qdesc[(size_t)i * 32], desc1 + (size_t)tb->q_idx1[i] * 32, 32);
+    qx[i] = kp1[tb->q_idx1[i]].x, qy[i] = kp1[tb->q_idx1[i]].y;
+  }
+  for (int p = 0; p < n_pairs; ++p)
+    if (pairs[p].n2 > 0) memcpy(&S.tdesc[(size_t)S.pair_base[p] * 32], pairs[p].desc2, (size_t)pairs[p].n2 * 32);
+  // one float block: qx | qy | tx | ty | f12 | sigma [| tangle]
+  std::vector<float>& fl = S.fl;
+  fl.insert(fl.end(), qx.begin(), qx.end());
+  fl.insert(fl.end(), qy.begin(), qy.end());
+  fl.insert(fl.end(), S.tx.begin(), S.tx.end());
+  fl.insert(fl.end(), S.ty.begin(), S.ty.end());
+  fl.insert(fl.end(), S.f12.begin(), S.f12.end());
+  fl.insert(fl.end(), S.sigma.begin(), S.sigma.end());
+  if (S.with_angles) fl.insert(fl.end(), S.tangle.begin(), S.tangle.end());
+  S.il = S.q_pair;
+  S.il.insert(S.il.end(), S.pair_base.begin(), S.pair_base.end());
+  RC(upload(m, S_QDESC, S.qdesc.data(), S.qdesc.size(), &S.d_qdesc));
+  RC(upload(m, S_TDESC, S.tdesc.data(), S.tdesc.size(), &S.d_tdesc));
+  RC(upload(m, S_TLEVEL, S.tlevel.data(), S.tlevel.size(), &S.d_tlevel));
+  RC(upload(m, S_START, tb->start.data(), tb->start.size(), &S.d_start));
+  RC(upload(m, S_CIDX, S.cidx.data(), S.cidx.size(), &S.d_cidx));
+  RC(upload(m, S_QPAIR, S.il.data(), S.il.size(), &S.d_il));
+  RC(upload(m, S_MISC, fl.data(), fl.size(), &S.d_fl));
+  RC(reserve(m, S_CAND, (size_t)S.total, &S.d_cand));
+  const float *d_qx = S.d_fl, *d_qy = d_qx + nq, *d_f12, *d_sigma;
+  S.d_tx = d_qy + nq, S.d_ty = S.d_tx + nt, d_f12 = S.d_ty + nt, d_sigma = d_f12 + S.f12.size(), S.d_tangle = d_sigma + S.sigma.size();
+  {
+    Profiler::Scope ps(&m->prof, "k_group_dist_pairs", m->stream);
+    launch_group_dist_pairs(m->stream, nq, S.total, S.d_start, S.d_cidx, S.d_qdesc, S.d_tdesc, S.d_tlevel, S.d_il, S.d_il + nq, d_f12, d_qx, d_qy, S.d_tx, S.d_ty,
+                            d_sigma, S.sig_stride, S.d_cand);
+  }
+  UVO_HIP_CHECK(hipGetLastError());
+  return UVO_OK;
+}
+
+// a caller's camera -> the device record; the level tables are copied in
+int tri_cam_pack(const uvo_triangulation_camera* c, TriCam* out) {
+  if (!c || !c->scale_factors || !c->sigma2) return fail(UVO_E_BADARG, "null camera");
+  if (c->nlevels < 1 || c->nlevels > kTriMaxLevels) return fail(UVO_E_BADARG, "camera: 1 <= nlevels <= 64");
+  memset(out, 0, sizeof(*out));
+  memcpy(out->r, c->rcw, sizeof(out->r));
+  memcpy(out->t, c->tcw, sizeof(out->t));
+  memcpy(out->ow, c->ow, sizeof(out->ow));
+  out->fx = c->fx, out->fy = c->fy, out->cx = c->cx, out->cy = c->cy;
+  memcpy(out->sf, c->scale_factors, (size_t)c->nlevels * sizeof(float));
+  memcpy(out->sigma2, c->sigma2, (size_t)c->nlevels * sizeof(float));
+  return UVO_OK;
+}
+int tri_check_octaves(const uvo_keypoint* kp, int n, int nlevels) {
+  for (int i = 0; i < n; ++i)
+    if (kp[i].octave < 0 || kp[i].octave >= nlevels) return fail(UVO_E_BADARG, "keypoint level outside the camera's level tables");
+  return UVO_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int uvo_search_for_triangulation_batch(uvo_matcher* m, const uvo_feature_vector* fv1, const uvo_keypoint* kp1, int n1, const uint8_t* desc1,
+                                       const uint8_t* has_mp1, int n_pairs, const uvo_triangulation_pair* pairs) {
+  if (!m) return fail(UVO_E_BADARG, "null handle");
+  tri_batch_free(m->tri_batch);
+  m->tri_batch = nullptr;
+  TriBatch* tb = new TriBatch();
+  struct Guard {
+    TriBatch* t;
+    ~Guard() { delete t; }
+  } guard{tb};
+  TriStage S;
+  RC(tri_stage_build(fv1, kp1, n1, desc1, has_mp1, n_pairs, pairs, false, tb, S));
+  if (S.total > 0) {
     UVO_HIP_CHECK(hipSetDevice(m->device));
-    // the uploads below read local staging vectors asynchronously: whatever way this block is left, the stream is drained first
-    struct Drain {
-      hipStream_t s;
-      bool armed;
-      ~Drain() {
-        if (armed) (void)hipStreamSynchronize(s);
-      }
-    } drain{m->stream, true};
-    std::vector<uint8_t> qdesc((size_t)nq * 32), tdesc(nt * 32);
-    std::vector<float> qx(nq), qy(nq);
-    for (int i = 0; i < nq; ++i) {
-      memcpy(&qdesc[(size_t)i * 32], desc1 + (size_t)tb->q_idx1[i] * 32, 32);
-      qx[i] = kp1[tb->q_idx1[i]].x, qy[i] = kp1[tb->q_idx1[i]].y;
-    }
-    for (int p = 0; p < n_pairs; ++p)
-      if (pairs[p].n2 > 0) memcpy(&tdesc[(size_t)pair_base[p] * 32], pairs[p].desc2, (size_t)pairs[p].n2 * 32);
-    // one float block: qx | qy | tx | ty | f12 | sigma
-    std::vector<float> fl;
-    fl.insert(fl.end(), qx.begin(), qx.end());
-    fl.insert(fl.end(), qy.begin(), qy.end());
-    fl.insert(fl.end(), tx.begin(), tx.end());
-    fl.insert(fl.end(), ty.begin(), ty.end());
-    fl.insert(fl.end(), f12.begin(), f12.end());
-    fl.insert(fl.end(), sigma.begin(), sigma.end());
-    std::vector<int32_t> il(q_pair);
-    il.insert(il.end(), pair_base.begin(), pair_base.end());
-    uint8_t *d_qdesc, *d_tdesc;
-    int32_t *d_tlevel, *d_start, *d_cidx, *d_il;
-    float* d_fl;
-    uint32_t* d_cand;
-    RC(upload(m, S_QDESC, qdesc.data(), qdesc.size(), &d_qdesc));
-    RC(upload(m, S_TDESC, tdesc.data(), tdesc.size(), &d_tdesc));
-    RC(upload(m, S_TLEVEL, tlevel.data(), tlevel.size(), &d_tlevel));
-    RC(upload(m, S_START, tb->start.data(), tb->start.size(), &d_start));
-    RC(upload(m, S_CIDX, cidx.data(), cidx.size(), &d_cidx));
-    RC(upload(m, S_QPAIR, il.data(), il.size(), &d_il));
-    RC(upload(m, S_MISC, fl.data(), fl.size(), &d_fl));
-    RC(reserve(m, S_CAND, (size_t)total, &d_cand));
-    const float *d_qx = d_fl, *d_qy = d_qx + nq, *d_tx = d_qy + nq, *d_ty = d_tx + nt, *d_f12 = d_ty + nt, *d_sigma = d_f12 + f12.size();
-    launch_group_dist_pairs(m->stream, nq, total, d_start, d_cidx, d_qdesc, d_tdesc, d_tlevel, d_il, d_il + nq, d_f12, d_qx, d_qy, d_tx, d_ty, d_sigma, sig_stride,
-                            d_cand);
-    UVO_HIP_CHECK(hipGetLastError());
-    UVO_HIP_CHECK(hipMemcpyAsync(tb->cand.data(), d_cand, (size_t)total * 4, hipMemcpyDeviceToHost, m->stream));
+    // the uploads below read the staging vectors asynchronously: whatever way this block is left, the stream is drained first
+    Drain drain{m->stream, true};
+    RC(tri_stage_launch(m, kp1, desc1, n_pairs, pairs, tb, S));
+    UVO_HIP_CHECK(hipMemcpyAsync(tb->cand.data(), S.d_cand, (size_t)S.total * 4, hipMemcpyDeviceToHost, m->stream));
     UVO_HIP_CHECK(hipStreamSynchronize(m->stream));  // the only host wait of the batch
     drain.armed = false;
   }
@@ -339,6 +396,118 @@ int uvo_fuse_batch(uvo_matcher* m, int n_targets, const uvo_fuse_target* targets
   UVO_HIP_CHECK(hipMemcpyAsync(best_dist, d_best + (size_t)n_targets * nmp, (size_t)n_targets * nmp * 4, hipMemcpyDeviceToHost, s));
   UVO_HIP_CHECK(hipStreamSynchronize(s));  // the only host wait of the batch
   drain.armed = false;
+  return UVO_OK;
+}
+
+int uvo_triangulate_matches(uvo_matcher* m, const uvo_triangulation_camera* cam1, const uvo_triangulation_camera* cam2, float ratio_factor,
+                            const uvo_keypoint* kp1, const uvo_keypoint* kp2, int n, int32_t* verdict, float* x3d) {
+  if (!m) return fail(UVO_E_BADARG, "null handle");
+  if (n < 0) return fail(UVO_E_BADARG, "bad sizes");
+  TriCam cams[2];
+  RC(tri_cam_pack(cam1, &cams[0]));
+  RC(tri_cam_pack(cam2, &cams[1]));
+  if (n == 0) return UVO_OK;
+  if (!kp1 || !kp2 || !verdict || !x3d) return fail(UVO_E_BADARG, "null pointer");
+  RC(tri_check_octaves(kp1, n, cam1->nlevels));
+  RC(tri_check_octaves(kp2, n, cam2->nlevels));
+  UVO_HIP_CHECK(hipSetDevice(m->device));
+  hipStream_t s = m->stream;
+  Drain drain{s, true};
+  TriCam* d_cams;
+  uvo_keypoint *d_kp1, *d_kp2;
+  int32_t* d_verdict;
+  float* d_x3d;
+  RC(upload(m, S_QR, cams, 2, &d_cams));
+  RC(upload(m, S_KP, kp1, (size_t)n, &d_kp1));
+  RC(upload(m, S_QDESC, kp2, (size_t)n, &d_kp2));
+  RC(reserve(m, S_MATCH, (size_t)n, &d_verdict));
+  RC(reserve(m, S_PX, (size_t)n * 3, &d_x3d));
+  {
+    Profiler::Scope ps(&m->prof, "k_triangulate", s);
+    launch_triangulate(s, n, d_cams, ratio_factor, d_kp1, d_kp2, d_verdict, d_x3d);
+  }
+  UVO_HIP_CHECK(hipGetLastError());
+  UVO_HIP_CHECK(hipMemcpyAsync(verdict, d_verdict, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+  UVO_HIP_CHECK(hipMemcpyAsync(x3d, d_x3d, (size_t)n * 12, hipMemcpyDeviceToHost, s));
+  UVO_HIP_CHECK(hipStreamSynchronize(s));
+  drain.armed = false;
+  return UVO_OK;
+}
+
+int uvo_create_new_map_points(uvo_matcher* m, const uvo_feature_vector* fv1, const uvo_keypoint* kp1, int n1, const uint8_t* desc1,
+                              const uint8_t* has_mp1, int n_pairs, const uvo_triangulation_pair* pairs, const uvo_triangulation_camera* cam1,
+                              const uvo_triangulation_camera* cams2, float ratio_factor, int check_orientation, const uvo_new_map_points* out) {
+  if (!m) return fail(UVO_E_BADARG, "null handle");
+  if (!out || !out->n_matches || !out->n_accepted) return fail(UVO_E_BADARG, "null output");
+  if (n_pairs > 0 && n1 > 0 && (!out->idx1 || !out->idx2 || !out->verdict || !out->x3d)) return fail(UVO_E_BADARG, "null output");
+  TriBatch tb;  // the lists live for this call only: nothing is kept in the handle
+  TriStage S;
+  RC(tri_stage_build(fv1, kp1, n1, desc1, has_mp1, n_pairs, pairs, true, &tb, S));
+  std::vector<TriCam> cams((size_t)n_pairs + 1);
+  RC(tri_cam_pack(cam1, &cams[0]));
+  if (n_pairs > 0 && !cams2) return fail(UVO_E_BADARG, "null camera");
+  RC(tri_check_octaves(kp1, n1, cam1->nlevels));
+  for (int p = 0; p < n_pairs; ++p) {
+    RC(tri_cam_pack(&cams2[p], &cams[1 + p]));
+    RC(tri_check_octaves(pairs[p].kp2, pairs[p].n2, cams2[p].nlevels));
+  }
+  for (int p = 0; p < n_pairs; ++p) out->n_matches[p] = 0, out->n_accepted[p] = 0;
+  if (out->has_mp1_out && n1 > 0) memcpy(out->has_mp1_out, has_mp1, (size_t)n1);
+  if (S.total == 0) return UVO_OK;  // no query has a candidate: no pair can match
+  const int nq = S.nq;
+  int max_n2 = 1, max_q = 1;
+  std::vector<int32_t> pair_tab((size_t)n_pairs * 4);
+  for (int p = 0; p < n_pairs; ++p) {
+    const TriBatch::Pair& Q = tb.pairs[p];
+    pair_tab[4 * p] = Q.q_begin, pair_tab[4 * p + 1] = Q.q_end, pair_tab[4 * p + 2] = Q.n2, pair_tab[4 * p + 3] = S.pair_base[p];
+    max_n2 = std::max(max_n2, Q.n2), max_q = std::max(max_q, Q.q_end - Q.q_begin);
+  }
+  UVO_HIP_CHECK(hipSetDevice(m->device));
+  hipStream_t s = m->stream;
+  std::vector<int32_t> h_outi((size_t)3 * nq + 2 * n_pairs);
+  std::vector<float> h_x3d((size_t)3 * nq);
+  Drain drain{s, true};
+  RC(tri_stage_launch(m, kp1, desc1, n_pairs, pairs, &tb, S));
+  TriChain A;
+  TriCam* d_cams;
+  uvo_keypoint* d_kp1;
+  int32_t *d_pair, *d_qidx, *d_outi;
+  RC(upload(m, S_QR, cams.data(), cams.size(), &d_cams));
+  RC(upload(m, S_KP, kp1, (size_t)n1, &d_kp1));
+  RC(upload(m, S_BLOCKED, has_mp1, (size_t)n1, &A.has_mp1));
+  RC(upload(m, S_QMIN, tb.q_idx1.data(), tb.q_idx1.size(), &d_qidx));
+  RC(upload(m, S_QMAX, pair_tab.data(), pair_tab.size(), &d_pair));
+  RC(reserve(m, S_OWNER, (size_t)max_n2, &A.owner));
+  RC(reserve(m, S_OWNER2, (size_t)max_n2, &A.owner_next));
+  RC(reserve(m, S_CHOICE, (size_t)max_q, &A.choice));
+  RC(reserve(m, S_MATCH, (size_t)n1, &A.match12));
+  RC(reserve(m, S_IDX0, (size_t)3 * nq + 2 * n_pairs, &d_outi));  // idx1 | idx2 | verdict | n_matches | n_accepted
+  RC(reserve(m, S_PX, (size_t)3 * nq, &A.x3d));
+  A.n_pairs = n_pairs, A.n1 = n1, A.check_orientation = check_orientation ? 1 : 0, A.ratio_factor = ratio_factor;
+  A.cams = d_cams, A.pair = d_pair, A.q_idx1 = d_qidx, A.cand_start = S.d_start, A.cand = S.d_cand, A.kp1 = d_kp1;
+  A.tx = S.d_tx, A.ty = S.d_ty, A.tangle = S.d_tangle, A.tlevel = S.d_tlevel;
+  A.out_idx1 = d_outi, A.out_idx2 = d_outi + nq, A.verdict = d_outi + 2 * (size_t)nq;
+  A.n_matches = d_outi + 3 * (size_t)nq, A.n_accepted = A.n_matches + n_pairs;
+  {
+    Profiler::Scope ps(&m->prof, "k_create_new_map_points", s);
+    launch_create_new_map_points(s, A);
+  }
+  UVO_HIP_CHECK(hipGetLastError());
+  UVO_HIP_CHECK(hipMemcpyAsync(h_outi.data(), d_outi, h_outi.size() * 4, hipMemcpyDeviceToHost, s));
+  UVO_HIP_CHECK(hipMemcpyAsync(h_x3d.data(), A.x3d, h_x3d.size() * 4, hipMemcpyDeviceToHost, s));
+  if (out->has_mp1_out) UVO_HIP_CHECK(hipMemcpyAsync(out->has_mp1_out, A.has_mp1, (size_t)n1, hipMemcpyDeviceToHost, s));
+  UVO_HIP_CHECK(hipStreamSynchronize(s));  // the only host wait of the loop
+  drain.armed = false;
+  for (int p = 0; p < n_pairs; ++p) {
+    const int nm = h_outi[(size_t)3 * nq + p], qb = tb.pairs[p].q_begin;
+    if (nm < 0 || nm > tb.pairs[p].q_end - qb || nm > n1) return fail(UVO_E_HIP, "device returned an impossible match count");
+    out->n_matches[p] = nm, out->n_accepted[p] = h_outi[(size_t)3 * nq + n_pairs + p];
+    const size_t o = (size_t)p * n1;
+    memcpy(out->idx1 + o, &h_outi[qb], (size_t)nm * 4);
+    memcpy(out->idx2 + o, &h_outi[(size_t)nq + qb], (size_t)nm * 4);
+    memcpy(out->verdict + o, &h_outi[(size_t)2 * nq + qb], (size_t)nm * 4);
+    memcpy(out->x3d + o * 3, &h_x3d[(size_t)3 * qb], (size_t)nm * 12);
+  }
   return UVO_OK;
 }
 
