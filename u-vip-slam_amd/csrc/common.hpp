@@ -88,6 +88,22 @@ struct FinalSlot {  // 16 B
   int32_t aux;      // FAST score for detected points
 };
 
+// A lane's device scratch (the layout list at the top of this file), typed: the launch wrappers take the struct and read the fields
+// they need, so that neighbours of one type cannot change places at a call site.
+struct LaneScratch {
+  uint8_t *pyr = nullptr, *blur = nullptr;
+  uint32_t *cand_xy = nullptr, *cand_sc = nullptr, *cand_lo = nullptr, *pstate = nullptr, *sel_xy = nullptr, *sel_sc = nullptr;
+  int32_t *cand_count = nullptr, *sel_count = nullptr, *n_final = nullptr, *cor_n = nullptr, *cursor = nullptr;
+  uint32_t* cor = nullptr;     // FAST corner lists, one region per k_fast_score wavefront
+  uint8_t* cell_hi = nullptr;  // per cell: owns an NMS survivor >= fastTh
+  // the lane's adaptive FAST mode: tpass[level] = threshold of the level's streaming pass (fastTh: threshold-adaptive two-pass form;
+  // min(fastTh, 7): one pass + vote); fstat = the fall-back-cell sums k_octree turns into next batch's tpass (octree.hip), then, at
+  // fstat + kMaxLevels, the length of cell_list; fcount = per (frame, level) counts of the batch in flight
+  int32_t *tpass = nullptr, *fstat = nullptr, *fcount = nullptr;
+  uint2* cell_list = nullptr;  // (cell, frame) of the fall-back cells of the batch in flight (k_fast_cells_list -> k_fast_cells)
+  FinalSlot* flist = nullptr;
+};
+
 const char* hip_err_set(hipError_t e, const char* what);
 #ifdef __HIPCC__
 // index of the calling wavefront inside its workgroup, as a scalar: the compiler cannot prove threadIdx.x >> 6 wave-uniform by
@@ -96,6 +112,8 @@ __device__ __forceinline__ int wave_in_block() { return __builtin_amdgcn_readfir
 #endif
 
 int fail(int code, const char* msg);  // records msg for uvo_last_error() and returns code
+// hipMalloc for every handle of the library: the one place where its failure becomes UVO_E_NOMEM / UVO_E_HIP (*p = NULL then)
+int dev_malloc(void** p, size_t bytes);
 
 #define UVO_HIP_CHECK(expr)                                   \
   do {                                                        \
@@ -104,6 +122,12 @@ int fail(int code, const char* msg);  // records msg for uvo_last_error() and re
       uvo::hip_err_set(_e, #expr);                            \
       return UVO_E_HIP;                                       \
     }                                                         \
+  } while (0)
+
+#define RC(call)                   \
+  do {                             \
+    const int _rc = (call);        \
+    if (_rc != UVO_OK) return _rc; \
   } while (0)
 
 // ---- kernel launch wrappers (defined in the .hip files) ----
@@ -118,12 +142,8 @@ int launch_pyr_tiles(hipStream_t s, uint8_t* d_pyr, int64_t pyr_block, const Pyr
                      Level0View l0, int first, int last, int ntiles, uint32_t lds_bytes, int threads, int rows, int batch);
 void launch_gauss7(hipStream_t s, const uint8_t* d_pyr, uint8_t* d_blur, int64_t pyr_block, const LevelGeom* d_lv, const Geom& g, int4 taps,
                    int batch, int sse2_rounding, Level0View l0);
-void launch_fast_score(hipStream_t s, const uint8_t* d_pyr, int64_t pyr_block, const Geom& g, int fast_th, const int32_t* d_tpass, uint32_t* d_cor,
-                       uint8_t* d_cell_hi, uint32_t* d_cand_xy, uint32_t* d_cand_sc, uint32_t* d_cand_lo, int64_t cand_block, int32_t* d_cursor, int batch,
-                       Level0View l0);
-void launch_fast_cells(hipStream_t s, const uint8_t* d_pyr, int64_t pyr_block, const Geom& g, const CellDesc* d_cells, const int32_t* d_flag_cell,
-                       const int32_t* d_tpass, const uint8_t* d_cell_hi, uint2* d_list, int32_t* d_n_list, uint32_t* d_cand_xy, uint32_t* d_cand_sc,
-                       int64_t cand_block, int32_t* d_cursor, int batch, Level0View l0);
+void launch_fast_score(hipStream_t s, const LaneScratch& d, const Geom& g, int fast_th, int batch, Level0View l0);
+void launch_fast_cells(hipStream_t s, const LaneScratch& d, const Geom& g, const CellDesc* d_cells, const int32_t* d_flag_cell, int batch, Level0View l0);
 void launch_grider(hipStream_t s, const uint8_t* d_img, int w, int h, int64_t stride, int num_features, int grid_x, int grid_y, int threshold,
                    int nms, uint8_t* d_score, uint32_t* d_lists, int32_t* d_counts, uvo_keypoint* d_out, int cap, int32_t* d_n_out);
 int fast_rows_per_seg(int batch);
@@ -132,21 +152,17 @@ int fast_flags_per_frame(const Geom& g);
 // Launch shape of the quad-tree kernel, per extractor handle (nothing process-global: handles on several devices and host
 // threads coexist in one process).  wide_max_problems: up to this many (frame, level) problems run as 1024-thread workgroups.
 struct OctLaunchState {
-  int wide_max_problems = 0;  // UVO_TUNE_OCT_WIDE_MAX (extractor.cpp sets the default)
+  int wide_max_problems = 0;  // UVO_TUNE_OCT_WIDE_MAX
 };
 bool octree_gauss_applies(const OctLaunchState& st, const Geom& g, int batch);
-void launch_octree_gauss(hipStream_t s, const LevelGeom* d_lv, const Geom& g, const uint8_t* d_pyr, uint8_t* d_blur, int64_t pyr_block, int4 taps, int sse2_rounding,
-                         const uint32_t* d_cand_lo, int32_t* d_cursor, int32_t* d_fcount, int32_t* d_n_cell_list, uint8_t* d_cell_hi, uint32_t* d_cand_xy,
-                         uint32_t* d_cand_sc, int64_t cand_block, int32_t* d_cand_count, uint32_t* d_pstate, uint32_t* d_sel_xy, uint32_t* d_sel_sc,
-                         int32_t* d_sel_count, int batch, Level0View l0, const uint16_t* d_oct_tab);
+void launch_octree_gauss(hipStream_t s, const LevelGeom* d_lv, const Geom& g, const LaneScratch& d, int4 taps, int sse2_rounding, int batch, Level0View l0,
+                         const uint16_t* d_oct_tab);
 int prepare_octree(const Geom& g);  // the part of the quad-tree launch that can fail (called before a batch's first kernel)
 // the path tables of the closed-form quad-tree (octree_pyramid.hpp: path_xbits / path_ybits) are a constant of a level's geometry: built on the
 // host once per geometry, g.lv[l].oct_tab_off entries into dst (uint16 each); the kernels copy a level's table into LDS instead of computing
 // it per (frame, level) problem
 void octree_fill_path_tables(const Geom& g, uint16_t* dst);
-int launch_octree(hipStream_t s, OctLaunchState& st, const LevelGeom* d_lv, const Geom& g, const uint32_t* d_cand_lo, int32_t* d_cursor,
-                   int32_t* d_fcount, int32_t* d_n_cell_list, uint8_t* d_cell_hi, uint32_t* d_cand_xy, uint32_t* d_cand_sc, int64_t cand_block, int32_t* d_cand_count, uint32_t* d_pstate,
-                   uint32_t* d_sel_xy, uint32_t* d_sel_sc, int32_t* d_sel_count, int batch, const uint16_t* d_oct_tab);
+int launch_octree(hipStream_t s, OctLaunchState& st, const LevelGeom* d_lv, const Geom& g, const LaneScratch& d, int batch, const uint16_t* d_oct_tab);
 // FAST mode feedback handed to k_assemble (its workgroup 0 sums the batch's fall-back cells and re-decides each level's mode)
 struct FastAdapt {
   const int32_t* fcount;  // [batch][nlevels] fall-back cells per (frame, level), written by k_octree
@@ -154,10 +170,8 @@ struct FastAdapt {
   int32_t* last;          // [kMaxLevels] the batch's sums, kept for uvo_extractor_fast_state
   int adapt, fast_th;
 };
-void launch_assemble(hipStream_t s, const LevelGeom* d_lv, const Geom& g, FastAdapt fa, const uint32_t* d_sel_xy, const uint32_t* d_sel_sc,
-                     const int32_t* d_sel_count,
-                     const uvo_keypoint* d_in_kp, const int32_t* d_n_in, int in_cap, int32_t* d_grid, int grid_rows, int grid_cols,
-                     int min_px_dist, int full_detect, const int32_t* d_nfn, FinalSlot* d_flist, int32_t* d_n_final, int batch);
+void launch_assemble(hipStream_t s, const LevelGeom* d_lv, const Geom& g, FastAdapt fa, const LaneScratch& d, const int32_t* d_n_in, int in_cap,
+                     int32_t* d_grid, int grid_rows, int grid_cols, int min_px_dist, int full_detect, const int32_t* d_nfn, int batch);
 void launch_occupancy_grid(hipStream_t s, const uvo_keypoint* d_in_kp, const int32_t* d_n_in, int in_cap, int min_px_dist, int grid_rows, int grid_cols,
                            int32_t* d_grid, int batch);
 void launch_knn2(hipStream_t s, int pairs, int max_q, const uint8_t* d_q, const int32_t* d_nq, int nq_fixed, int q_stride, const uint8_t* d_t,
@@ -210,12 +224,9 @@ void launch_rot_filter(hipStream_t s, int nq, const float* d_qangle, const float
 // vocabulary tree descent (bow.hip)
 void launch_bow_descend(hipStream_t s, const int32_t* d_child_start, const int32_t* d_children, const uint8_t* d_desc, const int32_t* d_word_id,
                         const double* d_weight, int L, const uint8_t* d_feat, int n, int levelsup, int32_t* d_word, double* d_w, int32_t* d_node);
-void launch_describe(hipStream_t s, const LevelGeom* d_lv, const Geom& g, const uint8_t* d_pyr, const uint8_t* d_blur, int64_t pyr_block,
-                     const FinalSlot* d_flist, const int32_t* d_n_final, const uvo_keypoint* d_in_kp, int in_cap, const float* d_pattern,
+void launch_describe(hipStream_t s, const LevelGeom* d_lv, const Geom& g, const LaneScratch& d, const uvo_keypoint* d_in_kp, int in_cap, const float* d_pattern,
                      const uint32_t* d_patch, uvo_keypoint* d_out_kp, uint8_t* d_out_desc, int cap, int32_t* d_n_out, int batch, Level0View l0);
-
-void launch_describe_direct(hipStream_t s, const LevelGeom* d_lv, const Geom& g, const uint8_t* d_pyr, const uint8_t* d_blur, int64_t pyr_block, const uint32_t* d_sel_xy,
-                            const uint32_t* d_sel_sc, const int32_t* d_sel_count, FastAdapt fa, const float* d_pattern, const uint32_t* d_patch,
+void launch_describe_direct(hipStream_t s, const LevelGeom* d_lv, const Geom& g, const LaneScratch& d, FastAdapt fa, const float* d_pattern, const uint32_t* d_patch,
                             uvo_keypoint* d_out_kp, uint8_t* d_out_desc, int cap, int32_t* d_n_out, int batch, Level0View l0);
 
 void launch_clahe(hipStream_t s, const uint8_t* d_src, int w, int h, int64_t stride, int64_t frame_stride, int batch, int tiles_x, int tiles_y,

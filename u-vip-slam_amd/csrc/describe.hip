@@ -583,34 +583,30 @@ void launch_occupancy_grid(hipStream_t s, const uvo_keypoint* d_in_kp, const int
   hipLaunchKernelGGL(k_occupancy_grid, dim3(batch), dim3(1024), 0, s, d_in_kp, in_cap > 0 ? d_n_in : nullptr, in_cap, min_px_dist, grid_rows, grid_cols, d_grid);
 }
 
-void launch_assemble(hipStream_t s, const LevelGeom* d_lv, const Geom& g, FastAdapt fa, const uint32_t* d_sel_xy, const uint32_t* d_sel_sc,
-                     const int32_t* d_sel_count, const uvo_keypoint* d_in_kp, const int32_t* d_n_in, int in_cap, int32_t* d_grid, int grid_rows,
-                     int grid_cols, int min_px_dist, int full_detect, const int32_t* d_nfn, FinalSlot* d_flist, int32_t* d_n_final,
-                     int batch) {
-  (void)d_in_kp;
+void launch_assemble(hipStream_t s, const LevelGeom* d_lv, const Geom& g, FastAdapt fa, const LaneScratch& d, const int32_t* d_n_in, int in_cap,
+                     int32_t* d_grid, int grid_rows, int grid_cols, int min_px_dist, int full_detect, const int32_t* d_nfn, int batch) {
   if (full_detect)
-    hipLaunchKernelGGL(k_assemble<false>, dim3(batch), dim3(256), 0, s, d_lv, g.nlevels, fa, d_sel_xy, d_sel_sc, g.sel_block, d_sel_count, d_n_in, in_cap,
-                       d_grid, grid_rows, grid_cols, min_px_dist, full_detect, d_nfn, d_flist, g.flist_cap, d_n_final);
+    hipLaunchKernelGGL(k_assemble<false>, dim3(batch), dim3(256), 0, s, d_lv, g.nlevels, fa, d.sel_xy, d.sel_sc, g.sel_block, d.sel_count, d_n_in, in_cap,
+                       d_grid, grid_rows, grid_cols, min_px_dist, full_detect, d_nfn, d.flist, g.flist_cap, d.n_final);
   else
-    hipLaunchKernelGGL(k_assemble<true>, dim3(batch), dim3(256), 0, s, d_lv, g.nlevels, fa, d_sel_xy, d_sel_sc, g.sel_block, d_sel_count, d_n_in, in_cap,
-                       d_grid, grid_rows, grid_cols, min_px_dist, full_detect, d_nfn, d_flist, g.flist_cap, d_n_final);
+    hipLaunchKernelGGL(k_assemble<true>, dim3(batch), dim3(256), 0, s, d_lv, g.nlevels, fa, d.sel_xy, d.sel_sc, g.sel_block, d.sel_count, d_n_in, in_cap,
+                       d_grid, grid_rows, grid_cols, min_px_dist, full_detect, d_nfn, d.flist, g.flist_cap, d.n_final);
 }
 
-void launch_describe(hipStream_t s, const LevelGeom* d_lv, const Geom& g, const uint8_t* d_pyr, const uint8_t* d_blur, int64_t pyr_block,
-                     const FinalSlot* d_flist, const int32_t* d_n_final, const uvo_keypoint* d_in_kp, int in_cap, const float* d_pattern,
+void launch_describe(hipStream_t s, const LevelGeom* d_lv, const Geom& g, const LaneScratch& d, const uvo_keypoint* d_in_kp, int in_cap, const float* d_pattern,
                      const uint32_t* d_patch, uvo_keypoint* d_out_kp, uint8_t* d_out_desc, int cap, int32_t* d_n_out, int batch, Level0View l0) {
   const int slots = g.flist_cap < cap ? g.flist_cap : cap;
-  hipLaunchKernelGGL(k_describe<false>, dim3((slots + DK_WAVES * DK_PER_WAVE - 1) / (DK_WAVES * DK_PER_WAVE), batch), dim3(64 * DK_WAVES), 0, s, d_lv, g.nlevels, d_pyr, d_blur, pyr_block, d_flist,
-                     g.flist_cap, d_n_final, d_in_kp, in_cap, d_pattern, d_patch, d_out_kp, d_out_desc, cap, d_n_out, l0, DirectSel{});
+  hipLaunchKernelGGL(k_describe<false>, dim3((slots + DK_WAVES * DK_PER_WAVE - 1) / (DK_WAVES * DK_PER_WAVE), batch), dim3(64 * DK_WAVES), 0, s, d_lv, g.nlevels, d.pyr,
+                     d.blur, g.pyr_block, d.flist, g.flist_cap, d.n_final, d_in_kp, in_cap, d_pattern, d_patch, d_out_kp, d_out_desc, cap, d_n_out, l0, DirectSel{});
 }
 
 // FullDetect without k_assemble (a frame or two): k_describe reads the quad-tree survivors itself
-void launch_describe_direct(hipStream_t s, const LevelGeom* d_lv, const Geom& g, const uint8_t* d_pyr, const uint8_t* d_blur, int64_t pyr_block, const uint32_t* d_sel_xy,
-                            const uint32_t* d_sel_sc, const int32_t* d_sel_count, FastAdapt fa, const float* d_pattern, const uint32_t* d_patch,
+void launch_describe_direct(hipStream_t s, const LevelGeom* d_lv, const Geom& g, const LaneScratch& d, FastAdapt fa, const float* d_pattern, const uint32_t* d_patch,
                             uvo_keypoint* d_out_kp, uint8_t* d_out_desc, int cap, int32_t* d_n_out, int batch, Level0View l0) {
   const int slots = g.flist_cap < cap ? g.flist_cap : cap;
-  const DirectSel ds{d_sel_xy, d_sel_sc, d_sel_count, g.sel_block, fa, batch};
-  hipLaunchKernelGGL(k_describe<true>, dim3((slots + DK_WAVES * DK_PER_WAVE - 1) / (DK_WAVES * DK_PER_WAVE), batch), dim3(64 * DK_WAVES), 0, s, d_lv, g.nlevels, d_pyr, d_blur, pyr_block,
+  const DirectSel ds{d.sel_xy, d.sel_sc, d.sel_count, g.sel_block, fa, batch};
+  hipLaunchKernelGGL(k_describe<true>, dim3((slots + DK_WAVES * DK_PER_WAVE - 1) / (DK_WAVES * DK_PER_WAVE), batch), dim3(64 * DK_WAVES), 0, s, d_lv, g.nlevels, d.pyr,
+                     d.blur, g.pyr_block,
                      (const FinalSlot*)nullptr, g.flist_cap, (const int32_t*)nullptr, (const uvo_keypoint*)nullptr, 0, d_pattern, d_patch, d_out_kp, d_out_desc, cap, d_n_out, l0, ds);
 }
 

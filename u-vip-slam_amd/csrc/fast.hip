@@ -802,20 +802,17 @@ FastLevels fast_levels(const Geom& g, int batch) {
 
 // scores + in-cell NMS per region; survivors to the candidate array / the low list of their (frame, level) (the per-cell vote: octree.hip).
 // d_tpass[level] = threshold of the level's streaming pass (the lane's adaptive state, see k_octree)
-void launch_fast_score(hipStream_t s, const uint8_t* d_pyr, int64_t pyr_block, const Geom& g, int fast_th, const int32_t* d_tpass, uint32_t* d_cor,
-                       uint8_t* d_cell_hi, uint32_t* d_cand_xy, uint32_t* d_cand_sc, uint32_t* d_cand_lo, int64_t cand_block, int32_t* d_cursor, int batch,
-                       Level0View l0) {
+void launch_fast_score(hipStream_t s, const LaneScratch& d, const Geom& g, int fast_th, int batch, Level0View l0) {
   const FastLevels L = fast_levels(g, batch);
   const dim3 grid((L.items_per_frame + UVO_FAST_WAVES - 1) / UVO_FAST_WAVES, batch);
-  hipLaunchKernelGGL(k_fast_score, grid, dim3(64 * UVO_FAST_WAVES), 0, s, d_pyr, pyr_block, L, d_tpass, fast_th, d_cor, d_cell_hi, d_cand_xy, d_cand_sc, d_cand_lo,
-                     cand_block, d_cursor, l0);
+  hipLaunchKernelGGL(k_fast_score, grid, dim3(64 * UVO_FAST_WAVES), 0, s, d.pyr, g.pyr_block, L, d.tpass, fast_th, d.cor, d.cell_hi, d.cand_xy,
+                     d.cand_sc, d.cand_lo, g.cand_block, d.cursor, l0);
 }
 
 // the sparse second pass at the literal 7 over the cells of threshold-adaptive levels that own no survivor (only needed when fastTh > 7):
 // list them, then redo them with a fixed grid of wavefronts (most of which leave at once on textured frames)
-void launch_fast_cells(hipStream_t s, const uint8_t* d_pyr, int64_t pyr_block, const Geom& g, const CellDesc* d_cells, const int32_t* d_flag_cell,
-                       const int32_t* d_tpass, const uint8_t* d_cell_hi, uint2* d_list, int32_t* d_n_list, uint32_t* d_cand_xy, uint32_t* d_cand_sc,
-                       int64_t cand_block, int32_t* d_cursor, int batch, Level0View l0) {
+void launch_fast_cells(hipStream_t s, const LaneScratch& d, const Geom& g, const CellDesc* d_cells, const int32_t* d_flag_cell, int batch, Level0View l0) {
+  int32_t* const d_n_list = d.fstat + kMaxLevels;  // (the list's length follows the per-level sums)
   const FastLevels L = fast_levels(g, batch);
   int max_roi = 0;
   for (int l = 0; l < g.nlevels; ++l) max_roi = std::max(max_roi, std::max(g.lv[l].wCell, g.lv[l].hCell) + 6);
@@ -823,25 +820,25 @@ void launch_fast_cells(hipStream_t s, const uint8_t* d_pyr, int64_t pyr_block, c
   if (batch <= UVO_FC_DIRECT_MAX) {  // a latency call: one launch, a wavefront per flag entry
     const dim3 grid((L.flags_per_frame + FC_WAVES - 1) / FC_WAVES, batch);
     if (small)
-      hipLaunchKernelGGL((k_fast_cells<48, true>), grid, dim3(64 * FC_WAVES), 0, s, d_pyr, pyr_block, L, d_cells, d_list, d_n_list, d_flag_cell, d_tpass, d_cell_hi, d_cand_xy,
-                         d_cand_sc, cand_block, d_cursor, l0);
+      hipLaunchKernelGGL((k_fast_cells<48, true>), grid, dim3(64 * FC_WAVES), 0, s, d.pyr, g.pyr_block, L, d_cells, d.cell_list, d_n_list, d_flag_cell, d.tpass, d.cell_hi, d.cand_xy,
+                         d.cand_sc, g.cand_block, d.cursor, l0);
     else
-      hipLaunchKernelGGL((k_fast_cells<66, true>), grid, dim3(64 * FC_WAVES), 0, s, d_pyr, pyr_block, L, d_cells, d_list, d_n_list, d_flag_cell, d_tpass, d_cell_hi, d_cand_xy,
-                         d_cand_sc, cand_block, d_cursor, l0);
+      hipLaunchKernelGGL((k_fast_cells<66, true>), grid, dim3(64 * FC_WAVES), 0, s, d.pyr, g.pyr_block, L, d_cells, d.cell_list, d_n_list, d_flag_cell, d.tpass, d.cell_hi, d.cand_xy,
+                         d.cand_sc, g.cand_block, d.cursor, l0);
     return;
   }
   hipLaunchKernelGGL(k_fast_cells_list, dim3((L.flags_per_frame + FCL_THREADS - 1) / FCL_THREADS, batch), dim3(FCL_THREADS), 0, s, d_flag_cell, L.flags_per_frame,
-                     g.nlevels, d_tpass, d_cell_hi, d_list, d_n_list, (int)std::min<int64_t>((int64_t)g.total_cells * batch, INT32_MAX));
+                     g.nlevels, d.tpass, d.cell_hi, d.cell_list, d_n_list, (int)std::min<int64_t>((int64_t)g.total_cells * batch, INT32_MAX));
   // a fixed grid that fills the chip once (seven / three workgroups of four wavefronts per CU: LDS); fewer when the batch cannot hold that many cells
   const int64_t max_items = (int64_t)g.total_cells * batch;
   const int waves = (int)std::min<int64_t>(max_items, 256 * (small ? 7 : 3) * FC_WAVES);
   const dim3 grid((waves + FC_WAVES - 1) / FC_WAVES);
   if (small)
-    hipLaunchKernelGGL((k_fast_cells<48, false>), grid, dim3(64 * FC_WAVES), 0, s, d_pyr, pyr_block, L, d_cells, d_list, d_n_list, d_flag_cell, d_tpass, d_cell_hi, d_cand_xy,
-                       d_cand_sc, cand_block, d_cursor, l0);
+    hipLaunchKernelGGL((k_fast_cells<48, false>), grid, dim3(64 * FC_WAVES), 0, s, d.pyr, g.pyr_block, L, d_cells, d.cell_list, d_n_list, d_flag_cell, d.tpass, d.cell_hi, d.cand_xy,
+                       d.cand_sc, g.cand_block, d.cursor, l0);
   else
-    hipLaunchKernelGGL((k_fast_cells<66, false>), grid, dim3(64 * FC_WAVES), 0, s, d_pyr, pyr_block, L, d_cells, d_list, d_n_list, d_flag_cell, d_tpass, d_cell_hi, d_cand_xy,
-                       d_cand_sc, cand_block, d_cursor, l0);
+    hipLaunchKernelGGL((k_fast_cells<66, false>), grid, dim3(64 * FC_WAVES), 0, s, d.pyr, g.pyr_block, L, d_cells, d.cell_list, d_n_list, d_flag_cell, d.tpass, d.cell_hi, d.cand_xy,
+                       d.cand_sc, g.cand_block, d.cursor, l0);
 }
 
 }  // namespace uvo

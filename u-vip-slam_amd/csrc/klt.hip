@@ -17,7 +17,7 @@
 #include <cstring>
 #include <vector>
 
-#include "common.hpp"
+#include "extractor_priv.hpp"
 #include "fundamental.hpp"
 #include "uvo_math.hpp"
 
@@ -402,9 +402,6 @@ int uvo_klt_build_pyramid(uvo_klt* k, int slot, const uint8_t* img, int width, i
 
 // The image is the result of the extractor handle's last uvo_clahe() call, still in HBM: no upload.  The extractor's stream is
 // ordered in front of this handle's stream by an event.
-extern "C" const uint8_t* uvo_extractor_clahe_internal(uvo_extractor* h, int* width, int* height);
-extern "C" hipStream_t uvo_extractor_stream_internal(uvo_extractor* h);
-extern "C" int uvo_extractor_device_internal(uvo_extractor* h);
 int uvo_klt_build_pyramid_from_extractor(uvo_klt* k, int slot, uvo_extractor* h, int* levels_built) {
   if (!k || !h) return fail(UVO_E_BADARG, "null pointer");
   if (slot < 0 || slot >= k->cfg.slots) return fail(UVO_E_BADARG, "slot outside 0..slots-1");

@@ -5,13 +5,9 @@
 #include <cstring>
 #include <vector>
 
+#include "extractor_priv.hpp"
 #include "matcher_priv.hpp"
 #include "uvo_math.hpp"
-
-extern "C" hipStream_t uvo_extractor_stream_internal(uvo_extractor* h);
-extern "C" int uvo_extractor_device_internal(uvo_extractor* h);
-extern "C" void uvo_extractor_add_follower_internal(uvo_extractor* h, uvo_matcher* m);
-extern "C" void uvo_extractor_drop_follower_internal(uvo_extractor* h, uvo_matcher* m);
 
 using namespace uvo;
 

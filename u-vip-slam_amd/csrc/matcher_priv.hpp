@@ -60,12 +60,6 @@ struct uvo_matcher {
 namespace uvo {
 void tri_batch_free(void* p);
 
-#define RC(call)                   \
-  do {                             \
-    const int _rc = (call);        \
-    if (_rc != UVO_OK) return _rc; \
-  } while (0)
-
 // device buffer of at least `bytes` in `slot` (contents undefined after growth).  Growth: bytes + bytes/2 + 256, after the handle's
 // stream has drained (the old buffer may still be read by enqueued work).
 inline int ensure(uvo_matcher* m, Slot slot, size_t bytes, void** out) {
@@ -77,12 +71,7 @@ inline int ensure(uvo_matcher* m, Slot slot, size_t bytes, void** out) {
       b = Buf();
     }
     const size_t want = bytes + bytes / 2 + 256;
-    hipError_t e = hipMalloc(&b.p, want);
-    if (e != hipSuccess) {
-      b.p = nullptr;
-      hip_err_set(e, "hipMalloc");
-      return e == hipErrorOutOfMemory ? UVO_E_NOMEM : UVO_E_HIP;
-    }
+    RC(dev_malloc(&b.p, want));
     b.cap = want;
   }
   *out = b.p;

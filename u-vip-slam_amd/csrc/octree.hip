@@ -307,9 +307,8 @@ int prepare_octree(const Geom& g) {
   return UVO_OK;
 }
 
-int launch_octree(hipStream_t s, OctLaunchState& st, const LevelGeom* d_lv, const Geom& g, const uint32_t* d_cand_lo, int32_t* d_cursor,
-                   int32_t* d_fcount, int32_t* d_n_cell_list, uint8_t* d_cell_hi, uint32_t* d_cand_xy, uint32_t* d_cand_sc, int64_t cand_block, int32_t* d_cand_count, uint32_t* d_pstate, uint32_t* d_sel_xy, uint32_t* d_sel_sc,
-                   int32_t* d_sel_count, int batch, const uint16_t* d_oct_tab) {
+int launch_octree(hipStream_t s, OctLaunchState& st, const LevelGeom* d_lv, const Geom& g, const LaneScratch& d, int batch, const uint16_t* d_oct_tab) {
+  int32_t* const d_n_cell_list = d.fstat + kMaxLevels;  // (the fall-back cell list's length follows the per-level sums)
   int M, Mp2, pyr_words;
   const size_t lds = octree_lds(g, M, Mp2, pyr_words);  // (prepare_octree has raised the kernel's limit for it)
   // The kernel is latency bound (a few dozen dependent phases per problem): the per-candidate state lives in registers,
@@ -330,12 +329,12 @@ int launch_octree(hipStream_t s, OctLaunchState& st, const LevelGeom* d_lv, cons
   }
 #endif
   if (wide)
-    hipLaunchKernelGGL(k_octree<1024>, dim3(batch, g.nlevels), dim3(threads), lds, s, d_lv, g.nlevels, M, Mp2, pyr_words, (int)oct_box_region_bytes(M, pyr_words), (int)lds, fast_levels(g, batch), d_cand_lo,
-                       d_cursor, d_fcount, d_n_cell_list, d_cell_hi, d_cand_xy, d_cand_sc, cand_block, d_cand_count, d_pstate, d_sel_xy, d_sel_sc, g.sel_block, d_sel_count, d_oct_tab);
+    hipLaunchKernelGGL(k_octree<1024>, dim3(batch, g.nlevels), dim3(threads), lds, s, d_lv, g.nlevels, M, Mp2, pyr_words, (int)oct_box_region_bytes(M, pyr_words), (int)lds, fast_levels(g, batch), d.cand_lo,
+                       d.cursor, d.fcount, d_n_cell_list, d.cell_hi, d.cand_xy, d.cand_sc, g.cand_block, d.cand_count, d.pstate, d.sel_xy, d.sel_sc, g.sel_block, d.sel_count, d_oct_tab);
   else
     hipLaunchKernelGGL(k_octree<OCT_THREADS>, dim3(batch, g.nlevels), dim3(threads), lds, s, d_lv, g.nlevels, M, Mp2, pyr_words, (int)oct_box_region_bytes(M, pyr_words), (int)lds, fast_levels(g, batch),
-                       d_cand_lo, d_cursor, d_fcount, d_n_cell_list, d_cell_hi, d_cand_xy, d_cand_sc, cand_block, d_cand_count, d_pstate, d_sel_xy, d_sel_sc, g.sel_block,
-                       d_sel_count, d_oct_tab);
+                       d.cand_lo, d.cursor, d.fcount, d_n_cell_list, d.cell_hi, d.cand_xy, d.cand_sc, g.cand_block, d.cand_count, d.pstate, d.sel_xy, d.sel_sc, g.sel_block,
+                       d.sel_count, d_oct_tab);
   return UVO_OK;
 }
 
@@ -351,26 +350,25 @@ bool octree_gauss_applies(const OctLaunchState& st, const Geom& g, int batch) {
          gauss7_blocks_per_frame(g, gauss7_rows_per_seg(batch)) >= (UVO_OCT_EVERY - 1) * g.nlevels;  // (the interleave needs UVO_OCT_EVERY - 1 blur workgroups per quad-tree problem)
 }
 
-void launch_octree_gauss(hipStream_t s, const LevelGeom* d_lv, const Geom& g, const uint8_t* d_pyr, uint8_t* d_blur, int64_t pyr_block, int4 taps, int sse2_rounding,
-                         const uint32_t* d_cand_lo, int32_t* d_cursor, int32_t* d_fcount, int32_t* d_n_cell_list, uint8_t* d_cell_hi, uint32_t* d_cand_xy,
-                         uint32_t* d_cand_sc, int64_t cand_block, int32_t* d_cand_count, uint32_t* d_pstate, uint32_t* d_sel_xy, uint32_t* d_sel_sc,
-                         int32_t* d_sel_count, int batch, Level0View l0, const uint16_t* d_oct_tab) {
+void launch_octree_gauss(hipStream_t s, const LevelGeom* d_lv, const Geom& g, const LaneScratch& d, int4 taps, int sse2_rounding, int batch, Level0View l0,
+                         const uint16_t* d_oct_tab) {
+  int32_t* const d_n_cell_list = d.fstat + kMaxLevels;  // (the fall-back cell list's length follows the per-level sums)
   int M, Mp2, pyr_words;
   const size_t lds = std::max(octree_lds(g, M, Mp2, pyr_words), (size_t)GS_LDS_BYTES);
   GaussArgs G;
-  G.pyr = d_pyr, G.blur = d_blur, G.pyr_block = pyr_block, G.taps = taps, G.batch = batch, G.l0 = l0;
+  G.pyr = d.pyr, G.blur = d.blur, G.pyr_block = g.pyr_block, G.taps = taps, G.batch = batch, G.l0 = l0;
   G.rows_per_seg = gauss7_rows_per_seg(batch), G.blocks_x = gauss7_blocks_per_frame(g, G.rows_per_seg);
   G.plans = gauss7_plans(g, G.rows_per_seg);
   const int n_oct = batch * g.nlevels;
   const dim3 grid(n_oct + G.blocks_x * batch);
   if (sse2_rounding)
     hipLaunchKernelGGL(k_octree_gauss<true>, grid, dim3(256), lds, s, n_oct, G, d_lv, g.nlevels, M, Mp2, pyr_words, (int)oct_box_region_bytes(M, pyr_words), (int)lds,
-                       fast_levels(g, batch), d_cand_lo, d_cursor, d_fcount, d_n_cell_list, d_cell_hi, d_cand_xy, d_cand_sc, cand_block, d_cand_count, d_pstate, d_sel_xy, d_sel_sc,
-                       g.sel_block, d_sel_count, d_oct_tab);
+                       fast_levels(g, batch), d.cand_lo, d.cursor, d.fcount, d_n_cell_list, d.cell_hi, d.cand_xy, d.cand_sc, g.cand_block, d.cand_count, d.pstate, d.sel_xy, d.sel_sc,
+                       g.sel_block, d.sel_count, d_oct_tab);
   else
     hipLaunchKernelGGL(k_octree_gauss<false>, grid, dim3(256), lds, s, n_oct, G, d_lv, g.nlevels, M, Mp2, pyr_words, (int)oct_box_region_bytes(M, pyr_words), (int)lds,
-                       fast_levels(g, batch), d_cand_lo, d_cursor, d_fcount, d_n_cell_list, d_cell_hi, d_cand_xy, d_cand_sc, cand_block, d_cand_count, d_pstate, d_sel_xy, d_sel_sc,
-                       g.sel_block, d_sel_count, d_oct_tab);
+                       fast_levels(g, batch), d.cand_lo, d.cursor, d.fcount, d_n_cell_list, d.cell_hi, d.cand_xy, d.cand_sc, g.cand_block, d.cand_count, d.pstate, d.sel_xy, d.sel_sc,
+                       g.sel_block, d.sel_count, d_oct_tab);
 }
 
 // the levels' path tables as the closed form builds them (octree_pyramid.hpp), for the kernels to copy

@@ -1,9 +1,9 @@
-// Per-launch device timing with HIP events on the stream the kernels are launched on.
+// Per-launch device timing with HIP events on the stream the kernels are launched on.  One Profiler per handle, driven by the handle's
+// one host thread: the records are in enqueue order, whatever stream (pipeline lane) a launch went to.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
 #include <cstdint>
 #include <cstdio>
 #include <string>
@@ -15,12 +15,7 @@ struct Profiler {
   struct Rec {
     const char* name;
     hipEvent_t a, b;
-    uint64_t seq;  // enqueue order across every Profiler of the process (a handle's pipeline lanes each own one; the report folds them)
   };
-  static uint64_t next_seq() {
-    static std::atomic<uint64_t> c{0};
-    return c.fetch_add(1, std::memory_order_relaxed);
-  }
   bool on = false;
   std::string only;  // when not empty: time launches of this kernel only (two event records per launch are not free)
   std::vector<Rec> recs;
@@ -56,9 +51,7 @@ struct Profiler {
     Scope(Profiler* p_, const char* name, hipStream_t s_) : p(p_), s(s_), active(p_->wants(name)) {
       r.name = name;
       r.a = r.b = nullptr;
-      r.seq = 0;
       if (active) {
-        r.seq = next_seq();
         r.a = p->take();
         r.b = p->take();
         (void)hipEventRecord(r.a, s);
@@ -77,7 +70,6 @@ struct Profiler {
   // lane's stream they ran in) and "name:period2_*" (half the start-to-start time of launches TWO apart: with two pipeline lanes taking
   // the batches in turn that is one lane's period per step -- consecutive launches belong to different lanes, whose phase is free).
   int report(char* names, int names_cap, float* ms, int32_t* launches, int cap, bool spread = true) {
-    std::stable_sort(recs.begin(), recs.end(), [](const Rec& x, const Rec& y) { return x.seq < y.seq; });
     std::vector<std::string> nm;
     std::vector<float> tt;
     std::vector<int> cc;

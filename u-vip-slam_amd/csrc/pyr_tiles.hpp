@@ -19,7 +19,7 @@
 
 namespace uvo {
 
-// resize coefficient tables, indexed by padded output coordinates (border reflection folded in); built by extractor.cpp
+// resize coefficient tables, indexed by padded output coordinates (border reflection folded in); built by extractor_geom.cpp
 struct ResizeCol {  // 8 B: left tap column, the two 11-bit weights scaled by 16 (a << 4 <= 32768); pad: window base / v_perm selector halves
   uint16_t sx, a0, a1, pad;
 };

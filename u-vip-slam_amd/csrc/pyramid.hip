@@ -68,7 +68,7 @@ __global__ __launch_bounds__(256) void k_pad_level0(const uint8_t* __restrict__ 
 
 // cv::resize INTER_LINEAR, 8-bit generic path: horizontal pass in 11-bit fixed point (INTER_RESIZE_COEF_SCALE
 // = 2048) into int, vertical pass ((b0*(r0>>4))>>16) + ((b1*(r1>>4))>>16) + 2) >> 2.  The coefficient tables are built
-// on the host exactly as resizeGeneric_ builds them (extractor.cpp) and are indexed by *padded* output coordinates,
+// on the host exactly as resizeGeneric_ builds them (extractor_geom.cpp: build_resize_tables) and are indexed by *padded* output coordinates,
 // i.e. the REFLECT_101 border is already folded into them: entry px of the column table holds (sx, a0, a1) of the
 // level column reflect(px-16) with the weights scaled by 16, entry py of the row table (sy0, sy1, b0, b1).
 // One thread = 4 output bytes x RZ_ROWS rows.  Each of the two source rows is fetched as three aligned dwords (the four tap

@@ -27,15 +27,7 @@
 #include <string>
 #include <vector>
 
-#include "common.hpp"
-
-extern "C" int uvo_extract_batch_submit_internal(uvo_extractor* h, int batch, int n_download, const uint8_t* imgs, int width, int height,
-                                                  ptrdiff_t stride, ptrdiff_t frame_stride, uvo_keypoint* out_kp, uint8_t* out_desc, int cap,
-                                                  int32_t* n_out, int* ticket, hipEvent_t after_kernels, const uint8_t** d_desc,
-                                                  const int32_t** d_n);
-extern "C" hipStream_t uvo_matcher_stream_internal(uvo_matcher* m);
-extern "C" int uvo_extractor_next_lane_internal(const uvo_extractor* h);
-extern "C" int uvo_extract_batch_done_internal(uvo_extractor* h, int ticket);
+#include "extractor_priv.hpp"
 
 using namespace uvo;
 

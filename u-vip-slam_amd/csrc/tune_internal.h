@@ -17,7 +17,10 @@
 /* (15: the side-stream blur of round 5, removed in round 6 -- a batch runs in ONE in-order stream) */
 #define UVO_TUNE_FEW_FRAMES 16      /* 1 (default): FullDetect batches of one or two frames run without k_assemble (k_describe reads the quad-tree's survivors
                                        itself: one launch less in a chain of latency-bound launches); 0: the same launches as large batches */
-#define UVO_TUNE_ZERO_COPY_OUT 17   /* 1 (default): host-buffer calls of up to 16 frames let k_describe write counts, keypoints and descriptors straight into
-                                       page-locked host memory (no device-to-host copies behind the last kernel); 0: staged in HBM and copied */
+#define UVO_TUNE_ZERO_COPY_OUT 17   /* 1 (default): host-buffer calls of up to 16 frames let the kernels read the call's small inputs from, and write counts,
+                                       keypoints and descriptors straight into, page-locked host memory (no small copies in front of the first kernel or
+                                       behind the last); 0: those calls take the staging of larger batches -- everything staged in HBM, copied to and from
+                                       the caller's (pageable) arrays, one wait for the counts and one for the records they size.  The same bytes; the one
+                                       knob whose non-default value costs more than it did while a page-locked bounce buffer stood between the two */
 #define UVO_TUNE_SPIN_WAIT 18       /* 1 (default): those calls, and uvo_extractor_synchronize() behind a batch of up to 16 frames, poll the stream (bounded
                                        busy wait) instead of sleeping on the completion interrupt; 0: hipStreamSynchronize */
