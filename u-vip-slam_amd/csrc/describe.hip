@@ -237,24 +237,34 @@ __device__ __forceinline__ int wave_sum(int v) {
   return v;
 }
 
-// 4 wavefronts per workgroup, DK_PER_WAVE consecutive final slots per wavefront.  The stages of a keypoint are a chain of
+// DK_WAVES wavefronts per workgroup, DK_PER_WAVE consecutive final slots per wavefront.  The stages of a keypoint are a chain of
 // dependent gathers (slot -> level geometry -> patch pixels -> angle -> steered sample points -> blurred pixels), so a
-// wavefront keeps several keypoints in flight: all patch loads are issued before the first reduction, all blurred-pixel
-// loads before the first ballot, and the pattern table is read once for the group.
+// wavefront keeps several keypoints in flight: all patch loads are issued before the first reduction, all blurred-window
+// loads before the first sample point, and the pattern table is read once for the group.
 constexpr int DK_PER_WAVE = 4;
 // The blurred plane is tiled (gauss.hip): 16 x 8-pixel tiles of one 128-byte line.  A keypoint's window (u in [-18, 21], v in [-18, 18])
 // lies inside a grid of at most 4 x 6 tiles; the tiles are copied whole -- one dwordx4 per lane, eight lanes per line -- into a
 // row-major LDS window of 48 rows x 64 bytes, from which the sample points are read as before.
 constexpr int DW_TX = 4, DW_TY = 6, DW_PITCH = DW_TX * 16, DW_ROWS = DW_TY * 8, DW_DWORDS = DW_ROWS * DW_PITCH / 4;
+// Stage C samples the group's windows one keypoint after the other, so a wavefront owns DK_WIN of them, not DK_PER_WAVE: keypoint
+// k + DK_WIN's tiles wait in registers (they are loaded with the others, in stage A) and take keypoint k's place once k is sampled.
+// 3 KB of LDS per wavefront instead of 12: the windows no longer hold the kernel to three wavefronts per SIMD, the register file
+// decides (tests/test_kernel_resources.py holds both figures).  Two windows are no faster than one (profiles/r08_describe_occupancy_ab.txt).
+constexpr int DK_WIN = 1;
 
+// Wavefronts per SIMD, held from both sides (amdgpu_waves_per_eu): two cost the kernel a third of its time, four are 3 % faster alone than the
+// three the 12 KB windows allowed and +1 % frames/s; five and six gain nothing more alone and take issue slots from the other pipeline lane's
+// k_fast_score (-1 % frames/s).  All in profiles/r08_describe_occupancy_ab.txt.
 #ifndef UVO_OCC_DESCRIBE
-#define UVO_OCC_DESCRIBE 1  // more workgroups per CU change nothing here (measured)
+#define UVO_OCC_DESCRIBE 4
 #endif
 #ifndef UVO_DESC_WAVES
-#define UVO_DESC_WAVES 2   // wavefronts per workgroup: 24.6 KB of LDS -- fits beside four k_fast_score workgroups of the other pipeline lane (a
-                           // four-wavefront workgroup's 49 KB only beside three): +2 % frames/s at 640x512, +-0 at 1920x1080
+#define UVO_DESC_WAVES 2   // wavefronts per workgroup (6 KB of LDS; four-wavefront workgroups: -1.5 % frames/s, one-wavefront ones -0.5 %)
 #endif
 constexpr int DK_WAVES = UVO_DESC_WAVES;
+// A tile row in registers: one dwordx4, held as ONE vector value.  (As a uint4 struct the compiler splits it into four scalars and then sinks the
+// loads of the waiting keypoints across stage B's basic blocks to their LDS stores in stage C: the window latency of three keypoints exposed.)
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 // DIRECT (FullDetect, a frame or two): there is no k_assemble launch in front -- the final list of a FullDetect frame is the levels' quad-tree
 // survivors one after the other (src/ORBextractor.cc:915-960), so a wavefront finds its slots' (level, index) from the eight survivor counts
 // itself: one stage less in a chain of latency-bound stages.  (With a batch that fills the chip the slot arithmetic in front of the dependent
@@ -268,7 +278,7 @@ struct DirectSel {
   int batch;
 };
 template <bool DIRECT>
-__global__ __launch_bounds__(64 * DK_WAVES, UVO_OCC_DESCRIBE) void k_describe(const LevelGeom* __restrict__ lv, int nlevels, const uint8_t* __restrict__ pyr,
+__global__ __attribute__((amdgpu_flat_work_group_size(64 * DK_WAVES, 64 * DK_WAVES), amdgpu_waves_per_eu(UVO_OCC_DESCRIBE, UVO_OCC_DESCRIBE))) void k_describe(const LevelGeom* __restrict__ lv, int nlevels, const uint8_t* __restrict__ pyr,
                                                   const uint8_t* __restrict__ blur, int64_t pyr_block,
                                                   const FinalSlot* __restrict__ flist, int flist_cap, const int32_t* __restrict__ n_final,
                                                   const uvo_keypoint* __restrict__ in_kp, int in_cap, const float* __restrict__ pattern,
@@ -307,8 +317,8 @@ __global__ __launch_bounds__(64 * DK_WAVES, UVO_OCC_DESCRIBE) void k_describe(co
   n = n > cap ? cap : n;
   if (slot0 >= n) return;
 
-  // blurred 37-row x 40-byte windows (u in [-18, 21], v in [-18, 18]) of the group's keypoints, wavefront-private
-  __shared__ uint32_t s_win[DK_WAVES][DK_PER_WAVE][DW_DWORDS];
+  // blurred 37-row x 40-byte windows (u in [-18, 21], v in [-18, 18]) of DK_WIN of the group's keypoints at a time, wavefront-private
+  __shared__ uint32_t s_win[DK_WAVES][DK_WIN][DW_DWORDS];
   uint32_t(*win)[DW_DWORDS] = s_win[wave_in_block()];
   uvo_keypoint kp[DK_PER_WAVE];
   int64_t center_off[DK_PER_WAVE];
@@ -317,7 +327,7 @@ __global__ __launch_bounds__(64 * DK_WAVES, UVO_OCC_DESCRIBE) void k_describe(co
   float scale[DK_PER_WAVE];
   bool rescale[DK_PER_WAVE], live[DK_PER_WAVE];
   uint32_t px[DK_PER_WAVE][4];
-  uint4 wv[DK_PER_WAVE][3];
+  u32x4 wv[DK_PER_WAVE][3];
   int wcy[DK_PER_WAVE], wcx[DK_PER_WAVE];  // (u, v) = (0, 0) inside the LDS window: row / byte column
   // tile rows of this lane: lane-load L = lane + 64 i covers row (L & 7) of tile (L >> 3) of the 4 x 6 grid, i.e. the 24 tiles are
   // spread over the three loads, eight lanes each
@@ -424,14 +434,15 @@ __global__ __launch_bounds__(64 * DK_WAVES, UVO_OCC_DESCRIBE) void k_describe(co
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
       const int ty = ty0 + (t_ty[i] < nty ? t_ty[i] : nty), tx = tx0 + (t_tx[i] < ntx ? t_tx[i] : ntx);
-      wv[k][i] = *reinterpret_cast<const uint4*>(bplane + ((int64_t)ty * tiles_x + tx) * 128 + ((lane & 7) << 4));
+      wv[k][i] = *reinterpret_cast<const u32x4*>(bplane + ((int64_t)ty * tiles_x + tx) * 128 + ((lane & 7) << 4));
     }
   }
+  // keypoint K's tiles -> window K % DK_WIN: tile (t_ty, t_tx), row lane & 7 -> LDS row t_ty * 8 + (lane & 7), bytes t_tx * 16 ..
+#define UVO_PUT_WINDOW(K)                                                                                                                       \
+  _Pragma("unroll") for (int i = 0; i < 3; ++i)                                                                                                 \
+      *reinterpret_cast<u32x4*>(reinterpret_cast<uint8_t*>(win[(K) % DK_WIN]) + (t_ty[i] * 8 + (lane & 7)) * DW_PITCH + t_tx[i] * 16) = wv[K][i];
 #pragma unroll
-  for (int k = 0; k < DK_PER_WAVE; ++k)
-#pragma unroll
-    for (int i = 0; i < 3; ++i)  // tile (t_ty, t_tx), row lane & 7 -> LDS row t_ty * 8 + (lane & 7), bytes t_tx * 16 ..
-      *reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(win[k]) + (t_ty[i] * 8 + (lane & 7)) * DW_PITCH + t_tx[i] * 16) = wv[k][i];
+  for (int k = 0; k < DK_WIN; ++k) { UVO_PUT_WINDOW(k) }
   // pattern: lane l evaluates pairs l, l+64, l+128, l+192
   float4 pq[4];
 #pragma unroll
@@ -504,12 +515,12 @@ __global__ __launch_bounds__(64 * DK_WAVES, UVO_OCC_DESCRIBE) void k_describe(co
   // of (u, v) = (0, 0) in the workgroup's LDS, in 16-bit arithmetic (negative rows / columns wrap and the sum comes out right).
   uint8_t t0[DK_PER_WAVE][4], t1[DK_PER_WAVE][4];
   const uint8_t* lds0 = reinterpret_cast<const uint8_t*>(&s_win[0][0][0]);
-  const uint32_t wave_base = (uint32_t)(wave_in_block() * DK_PER_WAVE * DW_DWORDS * 4);
+  const uint32_t wave_base = (uint32_t)(wave_in_block() * DK_WIN * DW_DWORDS * 4);
   float magic = 12582912.f;
   asm volatile("" : "+v"(magic));  // in a vector register: a fast-class instruction that reads a scalar register or a literal is a slow one
 #pragma unroll
   for (int k = 0; k < DK_PER_WAVE; ++k) {
-    uint32_t origin = wave_base + (uint32_t)(k * DW_DWORDS * 4 + wcy[k] * DW_PITCH + wcx[k]);
+    uint32_t origin = wave_base + (uint32_t)((k % DK_WIN) * DW_DWORDS * 4 + wcy[k] * DW_PITCH + wcx[k]);
     asm volatile("" : "+v"(origin));
     const float a = ca[k], b = sa[k];
     auto sample = [&](float x, float y) -> uint8_t {
@@ -525,7 +536,15 @@ __global__ __launch_bounds__(64 * DK_WAVES, UVO_OCC_DESCRIBE) void k_describe(co
       t0[k][j] = sample(pq[j].x, pq[j].y);
       t1[k][j] = sample(pq[j].z, pq[j].w);
     }
+    // the window is sampled: the keypoint DK_WIN further on takes it over (a wavefront's LDS instructions execute in order; the barriers keep
+    // the compiler from moving the stores above the reads)
+    if (k + DK_WIN < DK_PER_WAVE) {
+      __builtin_amdgcn_wave_barrier();
+      UVO_PUT_WINDOW(k + DK_WIN)
+      __builtin_amdgcn_wave_barrier();
+    }
   }
+#undef UVO_PUT_WINDOW
   // the group's descriptors are 128 consecutive bytes: the sixteen 64-bit ballots are dropped into lanes 0..15 (v_writelane takes the
   // scalar register the compare wrote) and leave in one store.  (s_nop 1: on gfx90a and later a vector instruction that reads a scalar
   // register must keep two wait states from the vector instruction that wrote it; the compiler inserts them for its own code only.)
