@@ -866,6 +866,40 @@ int uvo_klt_track_filtered(uvo_klt* k, int prev_slot, int next_slot, const float
  * indices, n_models [cap] (<= 0: the 7-point kernel gave none), scores [cap][3] (inlier counts, or LMedS medians; -1 where no model).
  * *n = hypotheses written. */
 int uvo_klt_fm_hypotheses(uvo_klt* k, int32_t* subsets, int32_t* n_models, double* scores, int cap, int* n);
+/*
+ * cv::solvePnPRansac(mappts, pts, mK, mDistCoef, Rvec, Tvec, false, iterations, reproj_err, conf, mask_pnp, cv::SOLVEPNP_EPNP) of
+ * Tracking::TrackWithPnP (src/Tracking.cc:1864: 300, 3, 0.99) on the device, in the handle's stream, scratch sized at uvo_klt_create
+ * (n <= max_points, iterations 1..1000; nothing allocated per call; one upload, one download).  OpenCV 3.4's semantics, recalled
+ * [OCV-RECALL, items 1-7 of tests/pnp_model.py]: 5 points per hypothesis drawn from cv::RNG seeded with (uint64)-1, only repeated
+ * indices redrawn; EPnP on the float-stored undistorted points; projectPoints + float error against reproj_err^2; a hypothesis is
+ * taken iff its count exceeds max(best, 4); EPnP once more on the winner's inliers in double; n == 5 solves once on all points.
+ *   obj, img : n x (X, Y, Z) and n x (u, v) float32 (Point3f / Point2f layout)
+ *   cam      : fisheye must be 0 (UVO_E_BADARG otherwise): solvePnPRansac applies the pin-hole model to mDistCoef whatever Fisheye_Cam
+ *              says, and so does this call
+ *   rvec, tvec : 3 doubles each; Tcw (may be NULL): the float 4 x 4 [R t; 0 1] that :1874-1878 builds, row-major
+ *   inliers  : room for n indices; info->inliers of them are written, ascending: the RANSAC winner's, not re-evaluated after the refit
+ *   info     : may be NULL.  ok = 0 (and zeros everywhere, no inliers) when n <= 4 (the else branch at :1866; the GPU is not touched),
+ *              when no hypothesis reaches 5 inliers or when a pose is not finite; NaN reproj_err or conf: UVO_E_BADARG
+ * Contract: the random stream, the scoring of a given pose, the replay of given counts and the inlier list are
+ * exact; the returned pose agrees with a correct EPnP on the returned inliers to the refit tolerance (from 6 inliers on) PROVIDED it
+ * orients the control-point axes the same way (largest component positive: a convention of this library, item 8 of the model's list,
+ * UNPINNED -- OpenCV's signs come out of its 3 x 3 SVD, and one flipped axis moves a noisy pose by 1e-4 .. 1e-2).  The pose
+ * of a single 5-point hypothesis is NOT part of the contract and cannot be: EPnP's system then has a two-dimensional null space whose
+ * basis is rounding noise of the eigen-solver, and the pose depends on it.  Such poses are held bit for bit to a host build of the same
+ * source (csrc/epnp_core.hpp) instead.
+ */
+typedef struct uvo_pnp_info {
+  int32_t ok;          /* a pose was found */
+  int32_t iterations;  /* OpenCV's iter at loop exit (0 for n == 5) */
+  int32_t inliers;     /* indices written */
+  uint32_t rng_draws;  /* cv::RNG::next() calls consumed */
+} uvo_pnp_info;
+int uvo_klt_solve_pnp_ransac(uvo_klt* k, const float* obj, const float* img, int n, const uvo_camera_model* cam, int iterations, double reproj_err,
+                             double conf, double* rvec, double* tvec, float* Tcw, int32_t* inliers, uvo_pnp_info* info);
+/* test tap: the hypotheses of the handle's last solve_pnp_ransac call, in draw order, up to its iterations: subsets [cap][5] point
+ * indices, poses [cap][12] (R row-major, t; zeros where EPnP gave no finite pose), counts [cap] (inliers; -1 where there is no pose).
+ * *n = hypotheses written. */
+int uvo_klt_pnp_hypotheses(uvo_klt* k, int32_t* subsets, double* poses, int32_t* counts, int cap, int* n);
 
 /* last HIP / argument error text for the calling thread's most recent failing call (never NULL) */
 const char* uvo_last_error(void);

@@ -5,7 +5,10 @@ extraction (tracked points pass through, the occupancy grid keeps new detections
 the C ABI; per-stage wall-clock (host buffers in/out) and a check of the final keypoints / descriptors against the oracle fed with
 the same tracked points.  The RANSAC stage of perform_matching (src/Tracking.cc:1062) is timed through the fused call
 (uvo_klt_track_filtered: tracker + undistortion + findFundamentalMat) on the same points, beside the chain: "track_filtered" is its
-wall-clock, "total_with_ransac" the frame with it in place of the plain tracker call.  Prints one JSON object."""
+wall-clock, "total_with_ransac" the frame with it in place of the plain tracker call.  The pose step that follows it in
+Tracking::TrackWithPnP (cv::solvePnPRansac, src/Tracking.cc:1864) is timed after the fused call on a synthetic scene with as many
+map points as the RANSAC kept ("solve_pnp_ransac"), and alone at 200 / 1000 / max_points points and inlier ratios 0.9 / 0.5
+("pnp_ms": median host-to-host time of 200 calls after 20 of warm-up).  Prints one JSON object."""
 import importlib
 import json
 import os
@@ -25,6 +28,7 @@ def main():
     uvo = importlib.import_module("u-vip-slam_amd")
     synth = importlib.import_module("u-vip-slam_amd.synth")
     import oracle_lib
+    import pnp_model as pm
     o = oracle_lib.Oracle()
     W, H, NF, MINPX = 640, 512, 1000, 20
     frames = [synth.make_frame(4242, W, H)]
@@ -46,7 +50,7 @@ def main():
         # "chain": the enhanced frame stays in HBM between the three calls (clahe without download, pyramid and extraction from it)
         chain = check == "chain"
         t = {"clahe": [], "pyramid": [], "track": [], "extract": []}
-        tf, nin = [], []
+        tf, nin, tp = [], [], []
         prev_pts = None
         for i, raw in enumerate(frames):
             t0 = time.perf_counter()
@@ -80,6 +84,11 @@ def main():
                 f = klt.track_filtered((i - 1) & 1, i & 1, prev_pts, cam)
                 tf.append(time.perf_counter() - t6)
                 nin.append(int(f[5].sum()))
+                if nin[-1] >= 5:      # the pose from the surviving points' map points
+                    _, obj, pts, _, _, _ = pm.scene(i, nin[-1], 0.9, 0.5, pm.PLAIN)
+                    t7 = time.perf_counter()
+                    klt.solve_pnp_ransac(obj, pts, cam)
+                    tp.append(time.perf_counter() - t7)
             if i >= 3:
                 t["clahe"].append(t1 - t0), t["pyramid"].append(t2 - t1), t["track"].append(t3 - t2), t["extract"].append(t5 - t4)
             if check:   # both the idle-GPU pass and the chained pass are checked against the oracle
@@ -92,8 +101,20 @@ def main():
         res[key]["track_filtered"] = round(float(np.median(tf[2:])) * 1e3, 3)
         res[key]["total_with_ransac"] = round(res[key]["total"] + res[key]["track_filtered"] - res[key]["track"], 3)
         res[key]["mean_ransac_inliers"] = round(float(np.mean(nin)), 1)
+        res[key]["solve_pnp_ransac"] = round(float(np.median(tp[2:])) * 1e3, 3) if len(tp) > 2 else None
+    pnp = {}
+    for n in (200, 1000, 4096):
+        for ratio in (0.9, 0.5):
+            _, obj, pts, _, _, _ = pm.scene(n, n, ratio, 0.5, pm.PLAIN)
+            ts = []
+            for r in range(220):
+                t0 = time.perf_counter()
+                info = klt.solve_pnp_ransac(obj, pts, cam)[4]
+                ts.append(time.perf_counter() - t0)
+            pnp["n%d_ratio%.1f" % (n, ratio)] = {"ms": round(float(np.median(ts[20:])) * 1e3, 3), "iterations": info.iterations, "inliers": info.inliers}
     out = {"workload": "640x512 sequence of 21 frames, CLAHE(4, 12x12) + KLT(21x21, 5 levels) + top-up ORB (1000 feats, fastTh 20, Px_distance 20)",
            "ms_per_frame": res,
+           "pnp_ms": pnp,
            "mean_tracked_points": round(float(np.mean(ntracked)), 1),
            "extraction_bit_exact_vs_oracle_given_the_same_tracked_points": bool(exact)}
     if os.environ.get("UVO_FF_PROFILE"):

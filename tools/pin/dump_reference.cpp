@@ -319,6 +319,43 @@ int main(int argc, char** argv) {
       put("klt_pts1", "f4", p1.data(), 4, {(size_t)n, 2});
       put("klt_status", "u1", status.data(), 1, {(size_t)n});
       put("klt_err", "f4", err.data(), 4, {(size_t)n});
+    } else if (kind == "pnp") {
+      // Tracking::TrackWithPnP's call (src/Tracking.cc:1864).  What this can pin: the inlier list's semantics, iterations through the
+      // inlier count, the refit (EPnP on the returned inliers in double, incl. the sign convention of the control-point axes: compare
+      // with tests/pnp_model.py refit() on the recorded inliers) and projectPoints; never a 5-point hypothesis pose.
+      std::string name, fobj, fimg;
+      int n, nd, iters;
+      double fx, fy, cx, cy, thr, conf;
+      ss >> name >> n >> iters >> thr >> conf >> fx >> fy >> cx >> cy >> nd;
+      cv::Mat K = cv::Mat::eye(3, 3, CV_32F), D(nd > 0 ? nd : 4, 1, CV_32F, cv::Scalar(0));
+      K.at<float>(0, 0) = (float)fx, K.at<float>(1, 1) = (float)fy, K.at<float>(0, 2) = (float)cx, K.at<float>(1, 2) = (float)cy;
+      for (int i = 0; i < nd; ++i) {
+        double v;
+        ss >> v;
+        D.at<float>(i) = (float)v;
+      }
+      ss >> fobj >> fimg;
+      std::vector<char> ro = slurp(in + "/" + fobj), ri = slurp(in + "/" + fimg);
+      std::vector<cv::Point3f> mappts(n);
+      std::vector<cv::Point2f> pts(n);
+      std::memcpy(mappts.data(), ro.data(), (size_t)n * 12);
+      std::memcpy(pts.data(), ri.data(), (size_t)n * 8);
+      cv::Mat Rvec = cv::Mat::zeros(3, 1, CV_64FC1), Tvec = cv::Mat::zeros(3, 1, CV_64FC1);  // stay zero when the call returns false
+      std::vector<int> mask_pnp;
+      const bool ok = cv::solvePnPRansac(mappts, pts, K, D, Rvec, Tvec, false, iters, (float)thr, conf, mask_pnp, cv::SOLVEPNP_EPNP);
+      const int32_t okv = ok ? 1 : 0;
+      std::vector<cv::Point2f> proj;
+      cv::projectPoints(mappts, Rvec, Tvec, K, D, proj);
+      cv::Mat Rm;
+      cv::Rodrigues(Rvec, Rm);
+      put("pnp_" + name + "_ok", "i4", &okv, 4, {1});
+      put("pnp_" + name + "_rvec", "f8", Rvec.data, 8, {3});
+      put("pnp_" + name + "_tvec", "f8", Tvec.data, 8, {3});
+      put("pnp_" + name + "_R", "f8", Rm.data, 8, {3, 3});
+      put("pnp_" + name + "_inliers", "i4", mask_pnp.data(), 4, {mask_pnp.size()});
+      put("pnp_" + name + "_proj", "f4", proj.data(), 4, {(size_t)n, 2});
+      put("pnp_" + name + "_obj", "f4", mappts.data(), 4, {(size_t)n, 3});
+      put("pnp_" + name + "_img", "f4", pts.data(), 4, {(size_t)n, 2});
     }
   }
   std::printf("pin_dump: done (%s)\n", g_out.c_str());

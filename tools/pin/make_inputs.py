@@ -127,6 +127,17 @@ def main():
     lines.append("undistort pinhole 0 %d 458.654 457.296 367.215 248.375 4 -0.28340811 0.07395907 0.00019359 1.76187114e-05 %s" % (len(upts), f))
     lines.append("undistort fisheye 1 %d 413.32595366596017 413.70198739483686 305.9507483284928 259.4439948946375 4 -0.06125568297136998 "
                  "-0.003796743395135256 0.027326634771204592 -0.030296403142887066 %s" % (len(upts), f))
+    # cv::solvePnPRansac(..., 300, 3, 0.99, ..., SOLVEPNP_EPNP) of Tracking::TrackWithPnP (src/Tracking.cc:1864): scenes of tests/pnp_model.py.
+    # all-inlier scenes of 6 .. 400 points pin the refit (incl. the sign of the control-point axes, item 8 of the model), n = 5 the direct
+    # path, the rest the inlier list and the statistics; a 5-point hypothesis pose cannot be pinned
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import pnp_model as pm
+    for k, (n, ratio, noise, camera) in enumerate([(5, 1.0, 0.3, pm.EUROC), (6, 1.0, 1.0, pm.EUROC), (8, 1.0, 1.0, pm.PLAIN), (20, 1.0, 1.0, pm.EUROC), (50, 1.0, 1.0, pm.PLAIN),
+                                                   (400, 1.0, 0.3, pm.EUROC), (64, 0.7, 0.3, pm.EUROC), (400, 0.95, 0.3, pm.PLAIN), (400, 0.5, 1.0, pm.EUROC),
+                                                   (1000, 0.3, 1.0, pm.EUROC)]):
+        cam, obj, img, _, _, _ = pm.scene(900 + k, n, ratio, noise, camera)
+        lines.append("pnp s%d %d 300 3 0.99 %r %r %r %r %d %s %s %s" % (k, n, cam.fx, cam.fy, cam.cx, cam.cy, cam.n_dist, " ".join("%r" % v for v in cam.k[:cam.n_dist]),
+                                                                        put("pnp_%d_obj" % k, obj), put("pnp_%d_img" % k, img)))
     with open(os.path.join(a.out, "cases.txt"), "w") as fh:
         fh.write("\n".join(lines) + "\n")
     print("wrote %d cases to %s" % (len(lines), a.out))

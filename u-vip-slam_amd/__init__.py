@@ -42,7 +42,7 @@ ABI_SYMBOLS = [
     "uvo_grider_fast", "uvo_clahe", "uvo_clahe_batch_device", "uvo_extractor_read_plane", "uvo_extractor_read_candidates", "uvo_extractor_profile", "uvo_extractor_profile_only", "uvo_extractor_kernel_times",
     "uvo_matcher_create", "uvo_matcher_destroy", "uvo_matcher_synchronize", "uvo_hamming_knn2", "uvo_hamming_knn2_batch_device",
     "uvo_hamming_matrix", "uvo_distinctive_descriptors", "uvo_search_by_projection", "uvo_match_windows", "uvo_match_groups",
-    "uvo_search_by_projection_kf", "uvo_search_by_bow", "uvo_search_for_triangulation", "uvo_search_for_triangulation_batch", "uvo_search_for_triangulation_next", "uvo_triangulate_matches", "uvo_create_new_map_points", "uvo_fuse", "uvo_fuse_batch", "uvo_project_points", "uvo_search_points_in_frustum", "uvo_sim3_decompose", "uvo_sim3_relative", "uvo_project_sim3", "uvo_search_by_projection_sim3", "uvo_search_by_sim3", "uvo_haloc_hash", "uvo_klt_create", "uvo_klt_destroy", "uvo_klt_build_pyramid", "uvo_klt_build_pyramid_from_extractor", "uvo_klt_read_level", "uvo_klt_track", "uvo_undistort_points", "uvo_klt_track_undistorted", "uvo_klt_find_fundamental", "uvo_klt_track_filtered", "uvo_klt_fm_hypotheses", "uvo_vocabulary_create", "uvo_vocabulary_destroy", "uvo_bow_transform", "uvo_matcher_wait_extractor", "uvo_extractor_wait_matcher", "uvo_matcher_attach_extractor", "uvo_matcher_profile",
+    "uvo_search_by_projection_kf", "uvo_search_by_bow", "uvo_search_for_triangulation", "uvo_search_for_triangulation_batch", "uvo_search_for_triangulation_next", "uvo_triangulate_matches", "uvo_create_new_map_points", "uvo_fuse", "uvo_fuse_batch", "uvo_project_points", "uvo_search_points_in_frustum", "uvo_sim3_decompose", "uvo_sim3_relative", "uvo_project_sim3", "uvo_search_by_projection_sim3", "uvo_search_by_sim3", "uvo_haloc_hash", "uvo_klt_create", "uvo_klt_destroy", "uvo_klt_build_pyramid", "uvo_klt_build_pyramid_from_extractor", "uvo_klt_read_level", "uvo_klt_track", "uvo_undistort_points", "uvo_klt_track_undistorted", "uvo_klt_find_fundamental", "uvo_klt_track_filtered", "uvo_klt_fm_hypotheses", "uvo_klt_solve_pnp_ransac", "uvo_klt_pnp_hypotheses", "uvo_vocabulary_create", "uvo_vocabulary_destroy", "uvo_bow_transform", "uvo_matcher_wait_extractor", "uvo_extractor_wait_matcher", "uvo_matcher_attach_extractor", "uvo_matcher_profile",
     "uvo_matcher_kernel_times", "uvo_last_error", "uvo_device_info",
 ]
 
@@ -258,6 +258,8 @@ def _load():
     lib.uvo_klt_track_filtered.argtypes = [vp, ci, ci, vp, vp, ci, ci, ci, ctypes.c_double, ctypes.c_double, vp, vp, vp, vp, vp, ctypes.c_double,
                                            ctypes.c_double, vp, vp]
     lib.uvo_klt_fm_hypotheses.argtypes = [vp, vp, vp, vp, ci, vp]
+    lib.uvo_klt_solve_pnp_ransac.argtypes = [vp, vp, vp, ci, vp, ci, ctypes.c_double, ctypes.c_double, vp, vp, vp, vp, vp]
+    lib.uvo_klt_pnp_hypotheses.argtypes = [vp, vp, vp, vp, ci, vp]
     lib.uvo_fuse.argtypes = [vp, vp, ci, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, ci, cf, vp, vp]
     lib.uvo_search_for_triangulation_batch.argtypes = [vp, vp, vp, ci, vp, vp, ci, vp]
     lib.uvo_search_for_triangulation_next.argtypes = [vp, ci, vp, ci, vp, vp]
@@ -1253,6 +1255,14 @@ class FmInfo(ctypes.Structure):
         return (self.method, self.iterations, self.inliers, self.rng_draws)
 
 
+class PnpInfo(ctypes.Structure):
+    """uvo_pnp_info."""
+    _fields_ = [("ok", ctypes.c_int32), ("iterations", ctypes.c_int32), ("inliers", ctypes.c_int32), ("rng_draws", ctypes.c_uint32)]
+
+    def astuple(self):
+        return (self.ok, self.iterations, self.inliers, self.rng_draws)
+
+
 class KltCfg(ctypes.Structure):
     """uvo_klt_cfg."""
     _fields_ = [("max_width", ctypes.c_int32), ("max_height", ctypes.c_int32), ("max_level", ctypes.c_int32), ("win_width", ctypes.c_int32),
@@ -1382,6 +1392,31 @@ class KLT:
         if rc:
             raise UvoError(rc, "uvo_klt_fm_hypotheses")
         return sub[:n.value].copy(), nm[:n.value].copy(), sc[:n.value].copy()
+
+    def solve_pnp_ransac(self, obj, img, cam, iterations=300, reproj_err=3.0, conf=0.99):
+        """uvo_klt_solve_pnp_ransac: cv::solvePnPRansac(obj, img, mK, mDistCoef, rvec, tvec, false, iterations, reproj_err, conf, inliers,
+        SOLVEPNP_EPNP) of Tracking::TrackWithPnP (src/Tracking.cc:1864) on the device; cam: CameraModel (pin-hole).
+        Returns (rvec float64[3], tvec float64[3], Tcw float32[4, 4], inliers int32[k] ascending, PnpInfo); info.ok == 0: no pose."""
+        a = np.ascontiguousarray(obj, np.float32).reshape(-1, 3)
+        b = np.ascontiguousarray(img, np.float32).reshape(-1, 2)
+        if len(a) != len(b):
+            raise ValueError("obj and img differ in length")
+        rvec, tvec, Tcw, inl, info = np.zeros(3), np.zeros(3), np.zeros((4, 4), np.float32), np.zeros(max(len(a), 1), np.int32), PnpInfo()
+        rc = lib.uvo_klt_solve_pnp_ransac(self._h, _ptr(a), _ptr(b), len(a), ctypes.byref(cam), int(iterations), float(reproj_err), float(conf),
+                                          _ptr(rvec), _ptr(tvec), _ptr(Tcw), _ptr(inl), ctypes.byref(info))
+        if rc:
+            raise UvoError(rc, "uvo_klt_solve_pnp_ransac")
+        return rvec, tvec, Tcw, inl[:info.inliers].copy(), info
+
+    def pnp_hypotheses(self):
+        """uvo_klt_pnp_hypotheses: the last solve_pnp_ransac call's hypotheses in draw order -- (subsets int32[h, 5], poses float64[h, 12]
+        (R row-major, t; zeros where EPnP gave no finite pose), counts int32[h] (-1 where there is no pose))."""
+        cap = FM_MAX_HYPOTHESES
+        sub, poses, cnt, n = np.zeros((cap, 5), np.int32), np.zeros((cap, 12)), np.zeros(cap, np.int32), ctypes.c_int()
+        rc = lib.uvo_klt_pnp_hypotheses(self._h, _ptr(sub), _ptr(poses), _ptr(cnt), cap, ctypes.byref(n))
+        if rc:
+            raise UvoError(rc, "uvo_klt_pnp_hypotheses")
+        return sub[:n.value].copy(), poses[:n.value].copy(), cnt[:n.value].copy()
 
 
 def DescriptorDistance(a, b):

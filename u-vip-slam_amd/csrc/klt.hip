@@ -19,6 +19,7 @@
 
 #include "extractor_priv.hpp"
 #include "fundamental.hpp"
+#include "pnp.hpp"
 #include "uvo_math.hpp"
 
 namespace uvo {
@@ -290,6 +291,8 @@ struct uvo_klt {
   std::vector<int> slot_w, slot_h, slot_levels;
   FmScratch fm;          // findFundamentalMat (fundamental.hip)
   int fm_iters = 0;      // iterations of the last find_fundamental / track_filtered call (the hypothesis tap)
+  PnpScratch pnp;        // solvePnPRansac (pnp.hip)
+  int pnp_iters = 0;     // iterations of the last solve_pnp_ransac call (its hypothesis tap)
 };
 
 static void klt_geometry(int w, int h, int bx, int by, int max_level, KltGeom& G, int64_t* img_bytes, int64_t* der_shorts) {
@@ -322,6 +325,7 @@ void uvo_klt_destroy(uvo_klt* k) {
   for (void* p : ptrs)
     if (p) hipFree(p);
   fm_free(k->fm);
+  pnp_free(k->pnp);
   if (k->h_pts) (void)hipHostFree(k->h_pts);
   if (k->stream) hipStreamDestroy(k->stream);
   delete k;
@@ -352,6 +356,10 @@ int uvo_klt_create(const uvo_klt_cfg* cfg, uvo_klt** out) {
     return fail(UVO_E_NOMEM, "KLT scratch allocation failed");
   }
   if (const int rc = fm_alloc(k->fm)) {
+    uvo_klt_destroy(k);
+    return rc;
+  }
+  if (const int rc = pnp_alloc(k->pnp, cfg->max_points)) {
     uvo_klt_destroy(k);
     return rc;
   }
@@ -621,6 +629,66 @@ int uvo_klt_fm_hypotheses(uvo_klt* k, int32_t* subsets, int32_t* n_models, doubl
   UVO_HIP_CHECK(hipMemcpy(subsets, k->fm.subsets, (size_t)m * 7 * 4, hipMemcpyDeviceToHost));
   UVO_HIP_CHECK(hipMemcpy(n_models, k->fm.nmodels, (size_t)m * 4, hipMemcpyDeviceToHost));
   UVO_HIP_CHECK(hipMemcpy(scores, k->fm.scores, (size_t)m * 3 * 8, hipMemcpyDeviceToHost));
+  return UVO_OK;
+}
+
+int uvo_klt_solve_pnp_ransac(uvo_klt* k, const float* obj, const float* img, int n, const uvo_camera_model* cam, int iterations, double reproj_err,
+                             double conf, double* rvec, double* tvec, float* Tcw, int32_t* inliers, uvo_pnp_info* info) {
+  if (!k) return fail(UVO_E_BADARG, "null handle");
+  if (n < 0 || n > k->cfg.max_points) return fail(UVO_E_BADARG, "point count outside 0..max_points");
+  if (!rvec || !tvec || (n > 0 && (!obj || !img || !inliers))) return fail(UVO_E_BADARG, "null pointer");
+  if (!(reproj_err == reproj_err) || !(conf == conf)) return fail(UVO_E_BADARG, "NaN threshold or confidence");
+  if (iterations < 1 || iterations > kFmCap) return fail(UVO_E_BADARG, "iterations outside 1..1000");
+  UndistortCam UC;
+  if (const int rc = check_camera_model(cam, UC)) return rc;
+  if (cam->fisheye) return fail(UVO_E_BADARG, "solvePnPRansac applies the pin-hole model: fisheye must be 0");
+  std::fill(rvec, rvec + 3, 0.), std::fill(tvec, tvec + 3, 0.);
+  if (Tcw) std::fill(Tcw, Tcw + 16, 0.f);
+  if (info) *info = uvo_pnp_info{0, 0, 0, 0};
+  k->pnp_iters = 0;
+  if (n < pnp::kModelPoints) return UVO_OK;  // TrackWithPnP :1863-1868: not called with 4 points or fewer
+  UVO_HIP_CHECK(hipSetDevice(k->cfg.device));
+  hipStream_t s = k->stream;
+  const PnpScratch& p = k->pnp;
+  const size_t N = (size_t)n;
+  std::memcpy(p.h_io, obj, N * 12);
+  std::memcpy(p.h_io + N * 12, img, N * 8);
+  UVO_HIP_CHECK(hipMemcpyAsync(p.io, p.h_io, N * 20, hipMemcpyHostToDevice, s));
+  pnp::Cam C;
+  C.fx = UC.fx, C.fy = UC.fy, C.cx = UC.cx, C.cy = UC.cy;
+  for (int i = 0; i < 8; ++i) C.k[i] = UC.k[i];
+  if (const int rc = pnp_enqueue(s, p, n, C, iterations, reproj_err, conf)) return rc;
+  UVO_HIP_CHECK(hipMemcpyAsync(p.h_io, p.out, sizeof(PnpOut) + N * 4, hipMemcpyDeviceToHost, s));
+  UVO_HIP_CHECK(hipStreamSynchronize(s));
+  PnpOut o;
+  std::memcpy(&o, p.h_io, sizeof o);
+  k->pnp_iters = o.iterations;
+  if (info) std::memcpy(info, &o, sizeof *info);
+  if (!o.ok) return UVO_OK;
+  std::memcpy(inliers, p.h_io + sizeof o, (size_t)o.inliers * 4);
+  pnp::rodrigues(o.R, rvec);  // on the host: acos is no shared-source function (epnp_core.hpp)
+  std::copy(o.t, o.t + 3, tvec);
+  if (Tcw) {
+    for (int i = 0; i < 3; ++i) {
+      for (int j = 0; j < 3; ++j) Tcw[4 * i + j] = (float)o.R[3 * i + j];
+      Tcw[4 * i + 3] = (float)o.t[i];
+    }
+    Tcw[15] = 1.f;
+  }
+  return UVO_OK;
+}
+
+int uvo_klt_pnp_hypotheses(uvo_klt* k, int32_t* subsets, double* poses, int32_t* counts, int cap, int* n) {
+  if (!k || !n) return fail(UVO_E_BADARG, "null pointer");
+  if (cap < 0) return fail(UVO_E_BADARG, "negative capacity");
+  const int m = std::min(cap, k->pnp_iters);
+  if (m > 0 && (!subsets || !poses || !counts)) return fail(UVO_E_BADARG, "null pointer");
+  *n = m;
+  if (m == 0) return UVO_OK;
+  UVO_HIP_CHECK(hipSetDevice(k->cfg.device));
+  UVO_HIP_CHECK(hipMemcpy(subsets, k->pnp.subsets, (size_t)m * 5 * 4, hipMemcpyDeviceToHost));
+  UVO_HIP_CHECK(hipMemcpy(poses, k->pnp.poses, (size_t)m * 12 * 8, hipMemcpyDeviceToHost));
+  UVO_HIP_CHECK(hipMemcpy(counts, k->pnp.counts, (size_t)m * 4, hipMemcpyDeviceToHost));
   return UVO_OK;
 }
 
