@@ -368,6 +368,8 @@ def test_hamming_knn2_and_matrix(uvo, oracle):
     o = oracle.knn2(q, t, mask)
     np.testing.assert_array_equal(idx0, o[0])
     np.testing.assert_array_equal(idx1, o[2])
+    np.testing.assert_array_equal(d0.astype(np.int32), np.where(o[0] < 0, 0xFFFF, o[1]))
+    np.testing.assert_array_equal(d1.astype(np.int32), np.where(o[2] < 0, 0xFFFF, o[3]))
     m.close()
 
 
