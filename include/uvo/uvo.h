@@ -901,6 +901,89 @@ int uvo_klt_solve_pnp_ransac(uvo_klt* k, const float* obj, const float* img, int
  * *n = hypotheses written. */
 int uvo_klt_pnp_hypotheses(uvo_klt* k, int32_t* subsets, double* poses, int32_t* counts, int cap, int* n);
 
+/* ------------------------------------------------------------------------------------------------
+ * PnPsolver -- replaces USLAM::PnPsolver (include/PnPsolver.h, src/PnPsolver.cc) as Tracking::Relocalisation uses it
+ * (src/Tracking.cc:2415-2441): one solver per candidate key frame, SetRansacParameters(0.99,10,300,4,0.5,5.991), then iterate(5,...)
+ * over the candidates in turn until one returns a pose.  Here the solvers live in a set, and ONE call iterates a list of them.
+ * ---------------------------------------------------------------------------------------------- */
+/*
+ * The reference draws its minimal sets with DUtils::Random::RandomInt, which is libc's rand(), and nothing ever seeds it: the process
+ * runs on srand(1).  The library evaluates hypotheses ahead of the loop it replays and must not consume draws the reference would not,
+ * so it never calls rand(): the caller owns this state and passes it to every iterate call.  Equal to glibc's srand / rand for seeds
+ * in [0, 2^31) (seed 0 behaves as seed 1, as in glibc); larger seeds are outside the contract.
+ */
+typedef struct uvo_glibc_rand {
+  int32_t r[34]; /* the last 34 words of the additive feedback sequence, as a ring */
+  int32_t k;     /* ring position of the next output */
+} uvo_glibc_rand;
+void uvo_glibc_srand(uvo_glibc_rand* g, uint32_t seed);
+int32_t uvo_glibc_rand_next(uvo_glibc_rand* g); /* rand(): 0 .. 2^31 - 1 */
+
+typedef struct uvo_pnpsolver_set uvo_pnpsolver_set;
+/* SetRansacParameters(probability, minInliers, maxIterations, minSet, epsilon, th2), src/PnPsolver.cc:122 */
+typedef struct uvo_pnpsolver_params {
+  double probability;
+  int32_t min_inliers, max_iterations, min_set; /* min_set 4..8 */
+  float epsilon, th2;
+} uvo_pnpsolver_params;
+/* what SetRansacParameters derives, and the solver's persistent counters */
+typedef struct uvo_pnpsolver_info {
+  int32_t n;            /* N: correspondences */
+  int32_t min_inliers;  /* mRansacMinInliers after the adjustment */
+  int32_t max_its;      /* mRansacMaxIts after the adjustment */
+  int32_t iterations;   /* mnIterations */
+  int32_t best_inliers; /* mnBestInliers */
+} uvo_pnpsolver_info;
+typedef struct uvo_pnpsolver_status {
+  int32_t touched;    /* iterate() was called on this solver (everything after the returning one is untouched) */
+  int32_t no_more;    /* bNoMore */
+  int32_t iterations; /* mnIterations afterwards */
+} uvo_pnpsolver_status;
+typedef struct uvo_pnpsolver_result {
+  int32_t returned;   /* position in ids[] of the solver that returned a pose, -1: none did */
+  int32_t solver;     /* its id, -1 */
+  int32_t n_inliers;  /* nInliers of that call */
+  int32_t refined;    /* 1: Refine()'s pose and set (:227-237), 0: the best hypothesis's at exhaustion (:245-255) */
+  float Tcw[16];      /* row-major 4 x 4, R and t rounded double -> float per element, last row 0 0 0 1; zeros when nothing returned */
+  uint32_t draws;     /* RandomInt calls consumed by this call: min_set x iterations performed, summed over the touched solvers */
+  int32_t pad_;
+  uvo_pnpsolver_status* status; /* caller's [n_ids], may be NULL */
+  uint8_t* inliers;   /* caller's byte mask vbInliers, as long as the returning solver's n_matches; may be NULL */
+  int32_t inliers_cap;/* its length: UVO_E_CAPACITY when the returning solver's n_matches exceeds it */
+  int32_t pad2_;
+} uvo_pnpsolver_result;
+
+/* A set lives on a uvo_klt handle: launches go to that handle's stream, and the set must be destroyed before it.  All scratch is
+ * sized here: max_solvers 1..64 solvers of up to max_points 4..16384 correspondences, 320 hypothesis slots per solver. */
+int uvo_pnpsolver_set_create(uvo_klt* k, int max_solvers, int max_points, uvo_pnpsolver_set** out);
+void uvo_pnpsolver_set_destroy(uvo_pnpsolver_set* s);
+int uvo_pnpsolver_set_clear(uvo_pnpsolver_set* s); /* forget every solver; ids start again at 0 */
+/*
+ * PnPsolver::PnPsolver(F, vpMapPointMatches) + SetRansacParameters.  The caller has walked vpMapPointMatches as :80-102 does:
+ *   p3d [n][3]   GetWorldPos() of match i's map point          p2d [n][2]  F.mvKeysUn[i].pt
+ *   sigma2 [n]   F.mvLevelSigma2[kp.octave]                     kp_index[n] i itself (mvKeyPointIndices), each in [0, n_matches)
+ *   n_matches    vpMapPointMatches.size()                       fx fy cx cy F's float intrinsics
+ * n may be anything from 0 to max_points: a solver with fewer points than its nMinInliers answers bNoMore and draws nothing.
+ * UVO_E_BADARG: NaN or out-of-range parameters (probability outside (0,1), min_set outside 4..8, max_iterations < 1), the set full.
+ */
+int uvo_pnpsolver_add(uvo_pnpsolver_set* s, const float* p3d, const float* p2d, const float* sigma2, const int32_t* kp_index, int n, int n_matches,
+                      float fx, float fy, float cx, float cy, const uvo_pnpsolver_params* params, int* id);
+int uvo_pnpsolver_query(uvo_pnpsolver_set* s, int id, uvo_pnpsolver_info* info);
+/*
+ * iterate(n_iterations, bNoMore, vbInliers, nInliers) on ids[0], ids[1], ... in order, stopping after the first that returns a
+ * non-empty Tcw (find() is n_iterations = the solver's max_its).  One upload, three launches, one download, nothing allocated.
+ * The iterations a solver runs before it returns or gives up do not depend on any result -- max(max_its - mnIterations, n_iterations),
+ * the loop condition being an OR (:183) -- so every subset of the call is drawn up front from *rng, every (solver, hypothesis) pair is
+ * evaluated in one grid, and the loop is replayed over the counts.  On return *rng has advanced by exactly result->draws outputs:
+ * what the reference's rand() would have produced by then.  Solver state (mnIterations, the best count, set and pose) persists, for
+ * the touched solvers only.  ids must not repeat within one call.  Semantics pinned to src/PnPsolver.cc by tests/pnpsolver_model.py;
+ * single-hypothesis poses (EPnP on 4 points) are held to the host build of the same source only.
+ */
+int uvo_pnpsolver_iterate(uvo_pnpsolver_set* s, const int32_t* ids, int n_ids, int n_iterations, uvo_glibc_rand* rng, uvo_pnpsolver_result* result);
+/* test tap: the hypotheses solver `id` consumed in the set's last iterate call, in draw order: subsets [cap][min_set], poses [cap][12]
+ * (R row-major, t; zeros where EPnP gave no finite pose), counts [cap].  *n = hypotheses written (0 for an untouched solver). */
+int uvo_pnpsolver_hypotheses(uvo_pnpsolver_set* s, int id, int32_t* subsets, double* poses, int32_t* counts, int cap, int* n);
+
 /* last HIP / argument error text for the calling thread's most recent failing call (never NULL) */
 const char* uvo_last_error(void);
 /* library + device description, e.g. "uvo 0.1 gfx950 AMD Instinct MI355X" */

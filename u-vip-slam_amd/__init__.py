@@ -43,6 +43,8 @@ ABI_SYMBOLS = [
     "uvo_matcher_create", "uvo_matcher_destroy", "uvo_matcher_synchronize", "uvo_hamming_knn2", "uvo_hamming_knn2_batch_device",
     "uvo_hamming_matrix", "uvo_distinctive_descriptors", "uvo_search_by_projection", "uvo_match_windows", "uvo_match_groups",
     "uvo_search_by_projection_kf", "uvo_search_by_bow", "uvo_search_for_triangulation", "uvo_search_for_triangulation_batch", "uvo_search_for_triangulation_next", "uvo_triangulate_matches", "uvo_create_new_map_points", "uvo_fuse", "uvo_fuse_batch", "uvo_project_points", "uvo_search_points_in_frustum", "uvo_sim3_decompose", "uvo_sim3_relative", "uvo_project_sim3", "uvo_search_by_projection_sim3", "uvo_search_by_sim3", "uvo_haloc_hash", "uvo_klt_create", "uvo_klt_destroy", "uvo_klt_build_pyramid", "uvo_klt_build_pyramid_from_extractor", "uvo_klt_read_level", "uvo_klt_track", "uvo_undistort_points", "uvo_klt_track_undistorted", "uvo_klt_find_fundamental", "uvo_klt_track_filtered", "uvo_klt_fm_hypotheses", "uvo_klt_solve_pnp_ransac", "uvo_klt_pnp_hypotheses", "uvo_vocabulary_create", "uvo_vocabulary_destroy", "uvo_bow_transform", "uvo_matcher_wait_extractor", "uvo_extractor_wait_matcher", "uvo_matcher_attach_extractor", "uvo_matcher_profile",
+    "uvo_glibc_srand", "uvo_glibc_rand_next", "uvo_pnpsolver_set_create", "uvo_pnpsolver_set_destroy", "uvo_pnpsolver_set_clear", "uvo_pnpsolver_add",
+    "uvo_pnpsolver_query", "uvo_pnpsolver_iterate", "uvo_pnpsolver_hypotheses",
     "uvo_matcher_kernel_times", "uvo_last_error", "uvo_device_info",
 ]
 
@@ -260,6 +262,18 @@ def _load():
     lib.uvo_klt_fm_hypotheses.argtypes = [vp, vp, vp, vp, ci, vp]
     lib.uvo_klt_solve_pnp_ransac.argtypes = [vp, vp, vp, ci, vp, ci, ctypes.c_double, ctypes.c_double, vp, vp, vp, vp, vp]
     lib.uvo_klt_pnp_hypotheses.argtypes = [vp, vp, vp, vp, ci, vp]
+    lib.uvo_glibc_srand.argtypes = [vp, ctypes.c_uint32]
+    lib.uvo_glibc_srand.restype = None
+    lib.uvo_glibc_rand_next.argtypes = [vp]
+    lib.uvo_glibc_rand_next.restype = ctypes.c_int32
+    lib.uvo_pnpsolver_set_create.argtypes = [vp, ci, ci, vp]
+    lib.uvo_pnpsolver_set_destroy.argtypes = [vp]
+    lib.uvo_pnpsolver_set_destroy.restype = None
+    lib.uvo_pnpsolver_set_clear.argtypes = [vp]
+    lib.uvo_pnpsolver_add.argtypes = [vp, vp, vp, vp, vp, ci, ci, cf, cf, cf, cf, vp, vp]
+    lib.uvo_pnpsolver_query.argtypes = [vp, ci, vp]
+    lib.uvo_pnpsolver_iterate.argtypes = [vp, vp, ci, ci, vp, vp]
+    lib.uvo_pnpsolver_hypotheses.argtypes = [vp, ci, vp, vp, vp, ci, vp]
     lib.uvo_fuse.argtypes = [vp, vp, ci, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, ci, cf, vp, vp]
     lib.uvo_search_for_triangulation_batch.argtypes = [vp, vp, vp, ci, vp, vp, ci, vp]
     lib.uvo_search_for_triangulation_next.argtypes = [vp, ci, vp, ci, vp, vp]
@@ -1261,6 +1275,145 @@ class PnpInfo(ctypes.Structure):
 
     def astuple(self):
         return (self.ok, self.iterations, self.inliers, self.rng_draws)
+
+
+class GlibcRand(ctypes.Structure):
+    """uvo_glibc_rand: glibc's srand / rand as a value the caller owns (the reference's DUtils::Random::RandomInt runs on it, never
+    seeded: srand(1)).  The library's iterate call advances it by exactly the draws the reference would have made."""
+    _fields_ = [("r", ctypes.c_int32 * 34), ("k", ctypes.c_int32)]
+
+    def __init__(self, seed=1):
+        super().__init__()
+        lib.uvo_glibc_srand(ctypes.byref(self), int(seed))
+
+    def next(self):
+        return lib.uvo_glibc_rand_next(ctypes.byref(self))
+
+    def copy(self):
+        g = GlibcRand.__new__(GlibcRand)
+        ctypes.memmove(ctypes.byref(g), ctypes.byref(self), ctypes.sizeof(GlibcRand))
+        return g
+
+    def state(self):
+        return bytes(self)
+
+
+class PnPsolverParams(ctypes.Structure):
+    """uvo_pnpsolver_params; the defaults are Relocalisation's SetRansacParameters(0.99,10,300,4,0.5,5.991)."""
+    _fields_ = [("probability", ctypes.c_double), ("min_inliers", ctypes.c_int32), ("max_iterations", ctypes.c_int32), ("min_set", ctypes.c_int32),
+                ("epsilon", ctypes.c_float), ("th2", ctypes.c_float)]
+
+    def __init__(self, probability=0.99, min_inliers=10, max_iterations=300, min_set=4, epsilon=0.5, th2=5.991):
+        super().__init__(probability, min_inliers, max_iterations, min_set, epsilon, th2)
+
+
+class PnPsolverInfo(ctypes.Structure):
+    """uvo_pnpsolver_info."""
+    _fields_ = [("n", ctypes.c_int32), ("min_inliers", ctypes.c_int32), ("max_its", ctypes.c_int32), ("iterations", ctypes.c_int32),
+                ("best_inliers", ctypes.c_int32)]
+
+
+class PnPsolverStatus(ctypes.Structure):
+    """uvo_pnpsolver_status."""
+    _fields_ = [("touched", ctypes.c_int32), ("no_more", ctypes.c_int32), ("iterations", ctypes.c_int32)]
+
+
+class PnPsolverResultC(ctypes.Structure):
+    """uvo_pnpsolver_result."""
+    _fields_ = [("returned", ctypes.c_int32), ("solver", ctypes.c_int32), ("n_inliers", ctypes.c_int32), ("refined", ctypes.c_int32),
+                ("Tcw", ctypes.c_float * 16), ("draws", ctypes.c_uint32), ("pad_", ctypes.c_int32), ("status", ctypes.c_void_p),
+                ("inliers", ctypes.c_void_p), ("inliers_cap", ctypes.c_int32), ("pad2_", ctypes.c_int32)]
+
+
+class PnPsolverResult:
+    """One iterate call: returned (position in ids, -1: none), solver (its id), n_inliers, refined, Tcw float32[4, 4], draws,
+    status int32[n_ids, 3] (touched, bNoMore, mnIterations), inliers uint8[n_matches of the returning solver] (empty when none)."""
+
+    def __init__(self, c, status, inliers):
+        self.returned, self.solver, self.n_inliers, self.refined, self.draws = c.returned, c.solver, c.n_inliers, c.refined, c.draws
+        self.Tcw = np.array(c.Tcw, np.float32).reshape(4, 4)
+        self.status, self.inliers = status, inliers
+
+
+class PnPsolverSet:
+    """USLAM::PnPsolver for Tracking::Relocalisation (src/Tracking.cc:2415-2517): the solvers of all candidate key frames in one set on
+    a KLT handle, iterate() over a list of them as one device call.  `_api` / `_prefix` exist so that the tests' host build of the same
+    source can be driven through this very class."""
+    _prefix = "uvo_pnpsolver_"
+
+    def __init__(self, klt, max_solvers, max_points, _api=None):
+        self._api = _api if _api is not None else lib
+        self._klt = klt   # the set launches in the handle's stream: keep it alive
+        self._h = ctypes.c_void_p()
+        self._n_matches = []
+        rc = self._f("set_create")(klt._h if klt is not None else None, max_solvers, max_points, ctypes.byref(self._h))
+        if rc:
+            raise UvoError(rc, "uvo_pnpsolver_set_create")
+
+    def _f(self, name):
+        return getattr(self._api, self._prefix + name)
+
+    def close(self):
+        if getattr(self, "_h", None) and self._api is not None:
+            self._f("set_destroy")(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def clear(self):
+        rc = self._f("set_clear")(self._h)
+        if rc:
+            raise UvoError(rc, "uvo_pnpsolver_set_clear")
+        self._n_matches = []
+
+    def add(self, p3d, p2d, sigma2, kp_index=None, n_matches=None, K=(1.0, 1.0, 0.0, 0.0), params=None):
+        """PnPsolver(F, vpMapPointMatches) + SetRansacParameters -> solver id.  kp_index defaults to 0..n-1, n_matches to n."""
+        a = np.ascontiguousarray(p3d, np.float32).reshape(-1, 3)
+        b = np.ascontiguousarray(p2d, np.float32).reshape(-1, 2)
+        sg = np.ascontiguousarray(sigma2, np.float32).reshape(-1)
+        kp = np.arange(len(a), dtype=np.int32) if kp_index is None else np.ascontiguousarray(kp_index, np.int32).reshape(-1)
+        if not (len(a) == len(b) == len(sg) == len(kp)):
+            raise ValueError("p3d, p2d, sigma2 and kp_index differ in length")
+        nm = len(a) if n_matches is None else int(n_matches)
+        prm = params if params is not None else PnPsolverParams()
+        sid = ctypes.c_int()
+        rc = self._f("add")(self._h, _ptr(a), _ptr(b), _ptr(sg), _ptr(kp), len(a), nm, K[0], K[1], K[2], K[3], ctypes.byref(prm), ctypes.byref(sid))
+        if rc:
+            raise UvoError(rc, "uvo_pnpsolver_add")
+        self._n_matches.append(nm)
+        return sid.value
+
+    def query(self, sid):
+        info = PnPsolverInfo()
+        rc = self._f("query")(self._h, sid, ctypes.byref(info))
+        if rc:
+            raise UvoError(rc, "uvo_pnpsolver_query")
+        return info
+
+    def iterate(self, ids, n_iterations, rng):
+        """iterate(n_iterations) on each id in order until one returns a pose; rng (GlibcRand) is advanced in place -> PnPsolverResult."""
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        status = np.zeros((len(ids), 3), np.int32)
+        cap = max([self._n_matches[i] for i in ids if 0 <= i < len(self._n_matches)] + [1])
+        mask = np.zeros(cap, np.uint8)
+        res = PnPsolverResultC()
+        res.status, res.inliers, res.inliers_cap = status.ctypes.data, mask.ctypes.data, cap
+        rc = self._f("iterate")(self._h, _ptr(ids), len(ids), int(n_iterations), ctypes.byref(rng), ctypes.byref(res))
+        if rc:
+            raise UvoError(rc, "uvo_pnpsolver_iterate")
+        return PnPsolverResult(res, status, mask[:self._n_matches[res.solver]].copy() if res.returned >= 0 else mask[:0].copy())
+
+    def find(self, sid, rng):
+        """PnPsolver::find: iterate(mRansacMaxIts)."""
+        return self.iterate([sid], self.query(sid).max_its, rng)
+
+    def hypotheses(self, sid, min_set=4, cap=1024):
+        """Test tap: (subsets int32[h, min_set], poses float64[h, 12], counts int32[h]) solver `sid` consumed in the last iterate call."""
+        sub, poses, cnt, n = np.zeros((cap, min_set), np.int32), np.zeros((cap, 12)), np.zeros(cap, np.int32), ctypes.c_int()
+        rc = self._f("hypotheses")(self._h, sid, _ptr(sub), _ptr(poses), _ptr(cnt), cap, ctypes.byref(n))
+        if rc:
+            raise UvoError(rc, "uvo_pnpsolver_hypotheses")
+        return sub[:n.value].copy(), poses[:n.value].copy(), cnt[:n.value].copy()
 
 
 class KltCfg(ctypes.Structure):

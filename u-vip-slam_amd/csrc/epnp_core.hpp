@@ -159,6 +159,24 @@ struct Points {
   }
 };
 
+// the same for a caller that holds pixel coordinates as they are (pnpsolver_core.hpp: PnPsolver::add_correspondence takes the
+// undistorted key point's float u, v): solve() and what it calls take either form
+struct PixelPoints {
+  const float* obj;  // [.][3]
+  const float* pix;  // [.][2]
+  const int32_t* idx;
+  int n;
+  double fu, fv, uc, vc;
+  PNP_HD void world(int i, double* p) const {
+    const int j = idx[i];
+    p[0] = obj[3 * j], p[1] = obj[3 * j + 1], p[2] = obj[3 * j + 2];
+  }
+  PNP_HD void pixel(int i, double* u, double* v) const {
+    const int j = idx[i];
+    *u = pix[2 * j], *v = pix[2 * j + 1];
+  }
+};
+
 // workspace of one solve, in doubles; element e of a workspace with stride S lives at w[e * S] (S > 1: the workspaces of S lanes
 // interleaved in LDS, so that the lanes of a wavefront touch neighbouring banks)
 enum : int {
@@ -319,8 +337,8 @@ PNP_HD void alphas_of(const Ws<S>& W, const double* p, double* a) {
 }
 
 // point i in the camera frame of start c: the barycentric combination of that start's control points
-template <int S>
-PNP_HD void camera_point(const Ws<S>& W, const Points& P, int c, int i, double* pc, double* pw) {
+template <int S, class Pts>
+PNP_HD void camera_point(const Ws<S>& W, const Pts& P, int c, int i, double* pc, double* pw) {
   double a[4];
   P.world(i, pw);
   alphas_of(W, pw, a);
@@ -367,8 +385,8 @@ PNP_HD void betas_of_start(const Ws<S>& W, int c) {
 }
 
 // everything between MtM and the three candidate sets of camera-frame control points; one lane
-template <int S>
-PNP_HD void solve_from_mtm(const Ws<S>& W, const Points& P) {
+template <int S, class Pts>
+PNP_HD void solve_from_mtm(const Ws<S>& W, const Pts& P) {
   jacobi_eig(W, W_MTM, W_EV, 12);
   unsigned used = 0;
   for (int s = 0; s < 4; ++s) {  // the four smallest eigenvalues, smallest first (always four valid columns, NaN or not)
@@ -450,8 +468,8 @@ PNP_HD void orientation(const Ws<S>& W, int c) {
 // EPnP on the points P with `lanes` cooperating callers (this one is `lane`), `sync` between phases.  out: R (9, row-major), t (3) of
 // the start with the smallest mean reprojection error whose pose is finite; returns whether there is one (out untouched if not).
 // Every lane returns the same value; lane 0 writes out.
-template <int S, class Sync>
-PNP_HD bool solve(const Ws<S>& W, const Points& P, int lane, int lanes, const Sync& sync, double* out) {
+template <int S, class Sync, class Pts>
+PNP_HD bool solve(const Ws<S>& W, const Pts& P, int lane, int lanes, const Sync& sync, double* out) {
   const int n = P.n;
   const double inv_n = 1. / (double)n;
   // 1. centroid = control point 0

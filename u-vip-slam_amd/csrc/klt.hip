@@ -20,6 +20,7 @@
 #include "extractor_priv.hpp"
 #include "fundamental.hpp"
 #include "pnp.hpp"
+#include "pnpsolver.hpp"
 #include "uvo_math.hpp"
 
 namespace uvo {
@@ -294,6 +295,11 @@ struct uvo_klt {
   PnpScratch pnp;        // solvePnPRansac (pnp.hip)
   int pnp_iters = 0;     // iterations of the last solve_pnp_ransac call (its hypothesis tap)
 };
+
+namespace uvo {  // what a PnPsolver set borrows from the handle it lives on (pnpsolver.hpp)
+hipStream_t klt_stream(const uvo_klt* k) { return k->stream; }
+int klt_device(const uvo_klt* k) { return k->cfg.device; }
+}  // namespace uvo
 
 static void klt_geometry(int w, int h, int bx, int by, int max_level, KltGeom& G, int64_t* img_bytes, int64_t* der_shorts) {
   G.bx = bx, G.by = by;
