@@ -984,6 +984,94 @@ int uvo_pnpsolver_iterate(uvo_pnpsolver_set* s, const int32_t* ids, int n_ids, i
  * (R row-major, t; zeros where EPnP gave no finite pose), counts [cap].  *n = hypotheses written (0 for an untouched solver). */
 int uvo_pnpsolver_hypotheses(uvo_pnpsolver_set* s, int id, int32_t* subsets, double* poses, int32_t* counts, int cap, int* n);
 
+/* ------------------------------------------------------------------------------------------------
+ * Sim3Solver -- replaces USLAM::Sim3Solver (include/Sim3Solver.h, src/Sim3Solver.cc) as LoopClosing::ComputeSim3 uses it
+ * (src/LoopClosing.cc:373-479): one solver per loop candidate, SetRansacParameters(0.99,2,300), then iterate(5,...) over the candidates
+ * in turn until one returns a similarity, whose R, t, s go to SearchBySim3 (uvo_sim3_relative, uvo_search_by_sim3 on the same handle).
+ * Here the solvers live in a set, and ONE call iterates a list of them.  The generator is uvo_glibc_rand, as for the PnPsolver.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct uvo_sim3solver_set uvo_sim3solver_set;
+/* SetRansacParameters(probability, minInliers, maxIterations), src/Sim3Solver.cc:114; the header's defaults are (0.99, 6, 300).
+ * probability in (0, 1), min_inliers >= 0, max_iterations 1..320 (the hypothesis slots a set holds per solver): UVO_E_BADARG otherwise. */
+typedef struct uvo_sim3solver_params {
+  double probability;
+  int32_t min_inliers, max_iterations;
+} uvo_sim3solver_params;
+/* what the constructor reads of one key frame: GetRotation(), GetTranslation(), GetCalibrationMatrix() */
+typedef struct uvo_sim3_keyframe {
+  float Rcw[9]; /* row-major */
+  float tcw[3];
+  float fx, fy, cx, cy;
+} uvo_sim3_keyframe;
+typedef struct uvo_sim3solver_info {
+  int32_t n;            /* N: correspondences */
+  int32_t max_its;      /* mRansacMaxIts after the adjustment */
+  int32_t iterations;   /* mnIterations */
+  int32_t best_inliers; /* mnBestInliers */
+} uvo_sim3solver_info;
+typedef struct uvo_sim3solver_status {
+  int32_t touched;    /* iterate() was called on this solver (everything after the returning one is untouched) */
+  int32_t no_more;    /* bNoMore */
+  int32_t iterations; /* mnIterations afterwards */
+} uvo_sim3solver_status;
+typedef struct uvo_sim3solver_result {
+  int32_t returned;   /* position in ids[] of the solver that returned a transform, -1: none did */
+  int32_t solver;     /* its id, -1 */
+  int32_t n_inliers;  /* nInliers of that call */
+  uint32_t draws;     /* RandomInt calls consumed by this call: 3 x iterations performed, summed over the touched solvers */
+  float T12[16];      /* mBestT12, row-major 4 x 4 [s R | t; 0 0 0 1]; zeros when nothing returned */
+  float R12[9];       /* mBestRotation, row-major */
+  float t12[3];       /* mBestTranslation */
+  float scale;        /* mBestScale */
+  int32_t pad_;
+  uvo_sim3solver_status* status; /* caller's [n_ids], may be NULL */
+  uint8_t* inliers;   /* caller's byte mask vbInliers, as long as the returning solver's n_matches, indexed through mvnIndices1; may be NULL */
+  int32_t inliers_cap;/* its length: UVO_E_CAPACITY when a listed solver's n_matches exceeds it */
+  int32_t pad2_;
+} uvo_sim3solver_result;
+
+/* A set lives on a uvo_matcher handle: launches go to that handle's stream and are counted by uvo_matcher_profile, and the set must be
+ * destroyed before the handle.  All scratch is sized here: max_solvers 1..64 solvers of up to max_points 3..16384 correspondences,
+ * 320 hypothesis slots per solver. */
+int uvo_sim3solver_set_create(uvo_matcher* m, int max_solvers, int max_points, uvo_sim3solver_set** out);
+void uvo_sim3solver_set_destroy(uvo_sim3solver_set* s);
+int uvo_sim3solver_set_clear(uvo_sim3solver_set* s); /* forget every solver; ids start again at 0 */
+/*
+ * Sim3Solver::Sim3Solver(pKF1, pKF2, vpMatched12) + SetRansacParameters.  The caller has walked vpMatched12 as :62-103 does; per
+ * kept correspondence:
+ *   x1w, x2w [n][3]          GetWorldPos() of pMP1 and pMP2
+ *   sigma2_1, sigma2_2 [n]   pKF->GetSigma2(kp.octave) of the key point in either key frame (0 .. 1e12)
+ *   index1 [n]               i1, the position in vpMatched12 (mvnIndices1), each in [0, n_matches)
+ *   n_matches                vpMatched12.size() (mN1)
+ * The library computes mvX3Dc1/2 = Rcw X + tcw, FromCameraToImage, the truncated thresholds (size_t)(9.210 sigma2) and mRansacMaxIts
+ * on the host, once.  n may be anything from 0 to max_points.  With n < 3 the reference would draw from an empty vector; here such a
+ * solver never iterates (bNoMore, no draws): the one deliberate departure.
+ */
+int uvo_sim3solver_add(uvo_sim3solver_set* s, const float* x1w, const float* x2w, const float* sigma2_1, const float* sigma2_2, const int32_t* index1,
+                       int n, int n_matches, const uvo_sim3_keyframe* kf1, const uvo_sim3_keyframe* kf2, const uvo_sim3solver_params* params, int* id);
+/* SetRansacParameters again (:114-138): mRansacMaxIts is derived anew, mnIterations is zeroed, the best so far is kept */
+int uvo_sim3solver_set_ransac_parameters(uvo_sim3solver_set* s, int id, const uvo_sim3solver_params* params);
+int uvo_sim3solver_query(uvo_sim3solver_set* s, int id, uvo_sim3solver_info* info);
+/*
+ * iterate(n_iterations, bNoMore, vbInliers, nInliers) on ids[0], ids[1], ... in order, stopping after the first that returns a
+ * transform.  One upload, three launches, one host wait, nothing allocated.  iterate's loop condition is an AND (:158), so a solver
+ * runs min(n_iterations, mRansacMaxIts - mnIterations) iterations unless it returns (none if N < mRansacMinInliers): every subset of
+ * the call is drawn up front from a copy of *rng, every (solver, hypothesis) pair is evaluated on the device, and the loop is replayed
+ * over the counts.  On return *rng has advanced by exactly result->draws outputs.  mnIterations and mnBestInliers persist, for the
+ * touched solvers only; a solver that returned can be entered again.  A hypothesis whose T12 or T21 is not finite counts zero
+ * inliers.  ids must not repeat within one call.  Semantics pinned to src/Sim3Solver.cc by tests/sim3_model.py.
+ * Departures from the reference: (1) a solver with n < 3 never iterates (see uvo_sim3solver_add); (2) mBestT12 / mBestRotation /
+ * mBestTranslation / mBestScale are handed out for the returning solver of a call only: the reference also moves them with every new
+ * best of a call that returns nothing, which ComputeSim3 never reads, and the library does not keep them (mnBestInliers it does keep);
+ * (3) max_iterations is at most 320.
+ */
+int uvo_sim3solver_iterate(uvo_sim3solver_set* s, const int32_t* ids, int n_ids, int n_iterations, uvo_glibc_rand* rng, uvo_sim3solver_result* result);
+/* Sim3Solver::find (:209-213): iterate(mRansacMaxIts) on one solver */
+int uvo_sim3solver_find(uvo_sim3solver_set* s, int id, uvo_glibc_rand* rng, uvo_sim3solver_result* result);
+/* test tap: the hypotheses solver `id` consumed in the set's last iterate call, in draw order: subsets [cap][3], T12 and T21 [cap][16]
+ * (zeros where the transform is not finite), counts [cap].  *n = hypotheses written (0 for an untouched solver). */
+int uvo_sim3solver_hypotheses(uvo_sim3solver_set* s, int id, int32_t* subsets, float* T12, float* T21, int32_t* counts, int cap, int* n);
+
 /* last HIP / argument error text for the calling thread's most recent failing call (never NULL) */
 const char* uvo_last_error(void);
 /* library + device description, e.g. "uvo 0.1 gfx950 AMD Instinct MI355X" */

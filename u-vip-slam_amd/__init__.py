@@ -45,6 +45,8 @@ ABI_SYMBOLS = [
     "uvo_search_by_projection_kf", "uvo_search_by_bow", "uvo_search_for_triangulation", "uvo_search_for_triangulation_batch", "uvo_search_for_triangulation_next", "uvo_triangulate_matches", "uvo_create_new_map_points", "uvo_fuse", "uvo_fuse_batch", "uvo_project_points", "uvo_search_points_in_frustum", "uvo_sim3_decompose", "uvo_sim3_relative", "uvo_project_sim3", "uvo_search_by_projection_sim3", "uvo_search_by_sim3", "uvo_haloc_hash", "uvo_klt_create", "uvo_klt_destroy", "uvo_klt_build_pyramid", "uvo_klt_build_pyramid_from_extractor", "uvo_klt_read_level", "uvo_klt_track", "uvo_undistort_points", "uvo_klt_track_undistorted", "uvo_klt_find_fundamental", "uvo_klt_track_filtered", "uvo_klt_fm_hypotheses", "uvo_klt_solve_pnp_ransac", "uvo_klt_pnp_hypotheses", "uvo_vocabulary_create", "uvo_vocabulary_destroy", "uvo_bow_transform", "uvo_matcher_wait_extractor", "uvo_extractor_wait_matcher", "uvo_matcher_attach_extractor", "uvo_matcher_profile",
     "uvo_glibc_srand", "uvo_glibc_rand_next", "uvo_pnpsolver_set_create", "uvo_pnpsolver_set_destroy", "uvo_pnpsolver_set_clear", "uvo_pnpsolver_add",
     "uvo_pnpsolver_query", "uvo_pnpsolver_iterate", "uvo_pnpsolver_hypotheses",
+    "uvo_sim3solver_set_create", "uvo_sim3solver_set_destroy", "uvo_sim3solver_set_clear", "uvo_sim3solver_add", "uvo_sim3solver_set_ransac_parameters",
+    "uvo_sim3solver_query", "uvo_sim3solver_iterate", "uvo_sim3solver_find", "uvo_sim3solver_hypotheses",
     "uvo_matcher_kernel_times", "uvo_last_error", "uvo_device_info",
 ]
 
@@ -274,6 +276,16 @@ def _load():
     lib.uvo_pnpsolver_query.argtypes = [vp, ci, vp]
     lib.uvo_pnpsolver_iterate.argtypes = [vp, vp, ci, ci, vp, vp]
     lib.uvo_pnpsolver_hypotheses.argtypes = [vp, ci, vp, vp, vp, ci, vp]
+    lib.uvo_sim3solver_set_create.argtypes = [vp, ci, ci, vp]
+    lib.uvo_sim3solver_set_destroy.argtypes = [vp]
+    lib.uvo_sim3solver_set_destroy.restype = None
+    lib.uvo_sim3solver_set_clear.argtypes = [vp]
+    lib.uvo_sim3solver_add.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp]
+    lib.uvo_sim3solver_set_ransac_parameters.argtypes = [vp, ci, vp]
+    lib.uvo_sim3solver_query.argtypes = [vp, ci, vp]
+    lib.uvo_sim3solver_iterate.argtypes = [vp, vp, ci, ci, vp, vp]
+    lib.uvo_sim3solver_find.argtypes = [vp, ci, vp, vp]
+    lib.uvo_sim3solver_hypotheses.argtypes = [vp, ci, vp, vp, vp, vp, ci, vp]
     lib.uvo_fuse.argtypes = [vp, vp, ci, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, ci, cf, vp, vp]
     lib.uvo_search_for_triangulation_batch.argtypes = [vp, vp, vp, ci, vp, vp, ci, vp]
     lib.uvo_search_for_triangulation_next.argtypes = [vp, ci, vp, ci, vp, vp]
@@ -1414,6 +1426,146 @@ class PnPsolverSet:
         if rc:
             raise UvoError(rc, "uvo_pnpsolver_hypotheses")
         return sub[:n.value].copy(), poses[:n.value].copy(), cnt[:n.value].copy()
+
+
+class Sim3SolverParams(ctypes.Structure):
+    """uvo_sim3solver_params; the defaults are ComputeSim3's SetRansacParameters(0.99,2,300) (src/LoopClosing.cc:410)."""
+    _fields_ = [("probability", ctypes.c_double), ("min_inliers", ctypes.c_int32), ("max_iterations", ctypes.c_int32)]
+
+    def __init__(self, probability=0.99, min_inliers=2, max_iterations=300):
+        super().__init__(probability, min_inliers, max_iterations)
+
+
+class Sim3KeyFrame(ctypes.Structure):
+    """uvo_sim3_keyframe: Rcw (row-major), tcw, fx, fy, cx, cy of one key frame."""
+    _fields_ = [("Rcw", ctypes.c_float * 9), ("tcw", ctypes.c_float * 3), ("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float),
+                ("cy", ctypes.c_float)]
+
+    @staticmethod
+    def make(Rcw, tcw, K):
+        kf = Sim3KeyFrame()
+        kf.Rcw[:] = [float(v) for v in np.asarray(Rcw, np.float32).reshape(9)]
+        kf.tcw[:] = [float(v) for v in np.asarray(tcw, np.float32).reshape(3)]
+        kf.fx, kf.fy, kf.cx, kf.cy = (float(np.float32(v)) for v in K)
+        return kf
+
+
+class Sim3SolverInfo(ctypes.Structure):
+    """uvo_sim3solver_info."""
+    _fields_ = [("n", ctypes.c_int32), ("max_its", ctypes.c_int32), ("iterations", ctypes.c_int32), ("best_inliers", ctypes.c_int32)]
+
+
+class Sim3SolverResultC(ctypes.Structure):
+    """uvo_sim3solver_result."""
+    _fields_ = [("returned", ctypes.c_int32), ("solver", ctypes.c_int32), ("n_inliers", ctypes.c_int32), ("draws", ctypes.c_uint32),
+                ("T12", ctypes.c_float * 16), ("R12", ctypes.c_float * 9), ("t12", ctypes.c_float * 3), ("scale", ctypes.c_float), ("pad_", ctypes.c_int32),
+                ("status", ctypes.c_void_p), ("inliers", ctypes.c_void_p), ("inliers_cap", ctypes.c_int32), ("pad2_", ctypes.c_int32)]
+
+
+class Sim3SolverResult:
+    """One iterate call: returned (position in ids, -1: none), solver (its id), n_inliers, draws, T12 float32[4, 4], R float32[3, 3],
+    t float32[3], s, status int32[n_ids, 3] (touched, bNoMore, mnIterations), inliers uint8[n_matches of the returning solver]."""
+
+    def __init__(self, c, status, inliers):
+        self.returned, self.solver, self.n_inliers, self.draws = c.returned, c.solver, c.n_inliers, c.draws
+        self.T12 = np.array(c.T12, np.float32).reshape(4, 4)
+        self.R, self.t, self.s = np.array(c.R12, np.float32).reshape(3, 3), np.array(c.t12, np.float32), np.float32(c.scale)
+        self.status, self.inliers = status, inliers
+
+
+class Sim3SolverSet:
+    """USLAM::Sim3Solver for LoopClosing::ComputeSim3 (src/LoopClosing.cc:373-479): the solvers of all loop candidates in one set on an
+    ORBmatcher handle, iterate() over a list of them as one device call.  `_api` / `_prefix` exist so that the tests' host build of the
+    same source can be driven through this very class."""
+    _prefix = "uvo_sim3solver_"
+
+    def __init__(self, matcher, max_solvers, max_points, _api=None):
+        self._api = _api if _api is not None else lib
+        self._matcher = matcher   # the set launches in the handle's stream: keep it alive
+        self._h = ctypes.c_void_p()
+        self._n_matches = []
+        rc = self._f("set_create")(matcher._h if matcher is not None else None, max_solvers, max_points, ctypes.byref(self._h))
+        if rc:
+            raise UvoError(rc, "uvo_sim3solver_set_create")
+
+    def _f(self, name):
+        return getattr(self._api, self._prefix + name)
+
+    def close(self):
+        if getattr(self, "_h", None) and self._api is not None:
+            self._f("set_destroy")(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def clear(self):
+        rc = self._f("set_clear")(self._h)
+        if rc:
+            raise UvoError(rc, "uvo_sim3solver_set_clear")
+        self._n_matches = []
+
+    def add(self, x1w, x2w, sigma2_1, sigma2_2, index1, n_matches, kf1, kf2, params=None):
+        """Sim3Solver(pKF1, pKF2, vpMatched12) + SetRansacParameters -> solver id.  kf1, kf2: (Rcw, tcw, (fx, fy, cx, cy)) or
+        Sim3KeyFrame; index1 defaults to 0..n-1, n_matches to n."""
+        a = np.ascontiguousarray(x1w, np.float32).reshape(-1, 3)
+        b = np.ascontiguousarray(x2w, np.float32).reshape(-1, 3)
+        s1 = np.ascontiguousarray(sigma2_1, np.float32).reshape(-1)
+        s2 = np.ascontiguousarray(sigma2_2, np.float32).reshape(-1)
+        ix = np.arange(len(a), dtype=np.int32) if index1 is None else np.ascontiguousarray(index1, np.int32).reshape(-1)
+        if not (len(a) == len(b) == len(s1) == len(s2) == len(ix)):
+            raise ValueError("x1w, x2w, sigma2_1, sigma2_2 and index1 differ in length")
+        nm = len(a) if n_matches is None else int(n_matches)
+        k1 = kf1 if isinstance(kf1, Sim3KeyFrame) else Sim3KeyFrame.make(*kf1)
+        k2 = kf2 if isinstance(kf2, Sim3KeyFrame) else Sim3KeyFrame.make(*kf2)
+        prm = params if params is not None else Sim3SolverParams()
+        sid = ctypes.c_int()
+        rc = self._f("add")(self._h, _ptr(a), _ptr(b), _ptr(s1), _ptr(s2), _ptr(ix), len(a), nm, ctypes.byref(k1), ctypes.byref(k2), ctypes.byref(prm),
+                            ctypes.byref(sid))
+        if rc:
+            raise UvoError(rc, "uvo_sim3solver_add")
+        self._n_matches.append(nm)
+        return sid.value
+
+    def set_ransac_parameters(self, sid, params):
+        rc = self._f("set_ransac_parameters")(self._h, sid, ctypes.byref(params))
+        if rc:
+            raise UvoError(rc, "uvo_sim3solver_set_ransac_parameters")
+
+    def query(self, sid):
+        info = Sim3SolverInfo()
+        rc = self._f("query")(self._h, sid, ctypes.byref(info))
+        if rc:
+            raise UvoError(rc, "uvo_sim3solver_query")
+        return info
+
+    def _call(self, name, ids, inliers_cap, *args):
+        status = np.zeros((len(ids), 3), np.int32)
+        cap = max([self._n_matches[i] for i in ids if 0 <= i < len(self._n_matches)] + [1]) if inliers_cap is None else int(inliers_cap)
+        mask = np.zeros(max(cap, 1), np.uint8)
+        res = Sim3SolverResultC()
+        res.status, res.inliers, res.inliers_cap = status.ctypes.data, mask.ctypes.data, cap
+        rc = self._f(name)(self._h, *args, ctypes.byref(res))
+        if rc:
+            raise UvoError(rc, "uvo_sim3solver_" + name)
+        return Sim3SolverResult(res, status, mask[:self._n_matches[res.solver]].copy() if res.returned >= 0 else mask[:0].copy())
+
+    def iterate(self, ids, n_iterations, rng, inliers_cap=None):
+        """iterate(n_iterations) on each id in order until one returns a transform; rng (GlibcRand) is advanced in place."""
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        return self._call("iterate", ids, inliers_cap, _ptr(ids), len(ids), int(n_iterations), ctypes.byref(rng))
+
+    def find(self, sid, rng):
+        """Sim3Solver::find: iterate(mRansacMaxIts)."""
+        return self._call("find", [sid], None, int(sid), ctypes.byref(rng))
+
+    def hypotheses(self, sid, cap=1024):
+        """Test tap: (subsets int32[h, 3], T12 float32[h, 16], T21 float32[h, 16], counts int32[h]) of the last iterate call."""
+        sub, t12, t21 = np.zeros((cap, 3), np.int32), np.zeros((cap, 16), np.float32), np.zeros((cap, 16), np.float32)
+        cnt, n = np.zeros(cap, np.int32), ctypes.c_int()
+        rc = self._f("hypotheses")(self._h, sid, _ptr(sub), _ptr(t12), _ptr(t21), _ptr(cnt), cap, ctypes.byref(n))
+        if rc:
+            raise UvoError(rc, "uvo_sim3solver_hypotheses")
+        return sub[:n.value].copy(), t12[:n.value].copy(), t21[:n.value].copy(), cnt[:n.value].copy()
 
 
 class KltCfg(ctypes.Structure):
