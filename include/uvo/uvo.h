@@ -1072,6 +1072,53 @@ int uvo_sim3solver_find(uvo_sim3solver_set* s, int id, uvo_glibc_rand* rng, uvo_
  * (zeros where the transform is not finite), counts [cap].  *n = hypotheses written (0 for an untouched solver). */
 int uvo_sim3solver_hypotheses(uvo_sim3solver_set* s, int id, int32_t* subsets, float* T12, float* T21, int32_t* counts, int cap, int* n);
 
+/*
+ * Initializer -- replaces USLAM::Initializer (include/Initializer.h, src/Initializer.cc) as Tracking::Initialize (src/Tracking.cc:1340)
+ * and the recovery path (:1582) use it: the constructor on the reference frame, then Initialize(current frame, matches) until it
+ * returns true.  ONE call draws the sets, evaluates every hypothesis against every match, decomposes the best F and triangulates
+ * every inlier under the four motions.  The generator is uvo_glibc_rand (the reference draws from the process's never-seeded rand(),
+ * the stream PnPsolver and Sim3Solver consume too); a call with n2 >= 8 consumes exactly 8 * iterations outputs.
+ * Only the F path is built: Initialize returns ReconstructF unconditionally (src/Initializer.cc:110; the ReconstructH branch is
+ * commented out and nothing FindHomography produces leaves the function), so FindHomography, ComputeH21, CheckHomography, ReconstructH
+ * and Re_CheckRT (whose only call is commented out, src/Tracking.cc:1591) do not exist here.
+ * Departures from the reference: (1) n2 < 8, where the reference's draw is undefined, returns "not initialised" and consumes no
+ * draws; (2) when no hypothesis scores above 0 the reference indexes an empty inlier vector: here that call returns "not initialised"
+ * with best = -1; (3) iterations is at most 1024; (4) the caller's generator takes the place of rand(); (5) the parallax order
+ * statistic of a set that holds a NaN is the value a total order gives.  Semantics pinned to src/Initializer.cc by
+ * tests/initializer_model.py; tolerance contract: DESIGN.md section 4.
+ */
+typedef struct uvo_initializer uvo_initializer;
+typedef struct uvo_initializer_result {
+  int32_t initialized;  /* the return value of Initialize */
+  int32_t best;         /* the hypothesis FindFundamental kept (strictly the first of the largest score), -1: none scored above 0 */
+  int32_t n_inliers;    /* inliers of F21 (N of ReconstructF) */
+  uint32_t draws;       /* generator outputs consumed */
+  int32_t deciding;     /* 0..3: the first CheckRT count that equals maxGood; -1 when CheckRT never ran */
+  int32_t n_good[4];    /* nGood1..4: (R1, t), (R2, t), (R1, -t), (R2, -t) */
+  float parallax[4];    /* parallax1..4 in degrees */
+  float score;          /* SF */
+  float R21[9], t21[3]; /* row-major; zeros unless initialized */
+  float F21[9];         /* zeros when best < 0 */
+  int32_t pad_;
+  uint8_t* inliers;      /* caller's n2 bytes, may be NULL: vbMatchesInliersF */
+  float* p3d;            /* caller's n2 x 3 floats, may be NULL: vP3D, indexed by the current frame's key; zeros unless initialized */
+  uint8_t* triangulated; /* caller's n2 bytes, may be NULL: vbTriangulated; zeros unless initialized */
+} uvo_initializer_result;
+/* max_keys: 8..16384 keys per frame.  The object launches in the uvo_klt handle's stream and must be destroyed before it. */
+int uvo_initializer_create(uvo_klt* k, int max_keys, uvo_initializer** out);
+void uvo_initializer_destroy(uvo_initializer* init);
+/* Initializer(ReferenceFrame, sigma, iterations): keys1_xy = mvKeysUn of the reference frame (n1 x (x, y), 1 <= n1 <= max_keys), cam's
+ * fx, fy, cx, cy = mK; (1.0, 200) at the call sites; 1 <= iterations <= 1024, sigma > 0.  May be called again at any time. */
+int uvo_initializer_set_reference(uvo_initializer* init, const float* keys1_xy, int n1, const uvo_camera_model* cam, float sigma, int iterations);
+/* Initialize(CurrentFrame, vMatches12, ...): keys2_xy = mvKeysUn of the current frame (n2 <= max_keys), matches12[i] = the reference
+ * key of current key i (src/Initializer.cc:51-59: every i is a match, there is no >= 0 test; two may name the same reference key).
+ * An entry outside 0..n1-1: UVO_E_BADARG.  On return *rng has advanced by exactly result->draws outputs. */
+int uvo_initializer_initialize(uvo_initializer* init, const float* keys2_xy, int n2, const int32_t* matches12, uvo_glibc_rand* rng,
+                               uvo_initializer_result* result);
+/* test tap: every set of the last initialize call, its F21i and its score, in draw order: subsets [cap][8], F [cap][9], scores [cap].
+ * *n = hypotheses written (0 after a call with n2 < 8). */
+int uvo_initializer_hypotheses(uvo_initializer* init, int32_t* subsets, float* F, float* scores, int cap, int* n);
+
 /* last HIP / argument error text for the calling thread's most recent failing call (never NULL) */
 const char* uvo_last_error(void);
 /* library + device description, e.g. "uvo 0.1 gfx950 AMD Instinct MI355X" */

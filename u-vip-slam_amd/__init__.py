@@ -47,6 +47,7 @@ ABI_SYMBOLS = [
     "uvo_pnpsolver_query", "uvo_pnpsolver_iterate", "uvo_pnpsolver_hypotheses",
     "uvo_sim3solver_set_create", "uvo_sim3solver_set_destroy", "uvo_sim3solver_set_clear", "uvo_sim3solver_add", "uvo_sim3solver_set_ransac_parameters",
     "uvo_sim3solver_query", "uvo_sim3solver_iterate", "uvo_sim3solver_find", "uvo_sim3solver_hypotheses",
+    "uvo_initializer_create", "uvo_initializer_destroy", "uvo_initializer_set_reference", "uvo_initializer_initialize", "uvo_initializer_hypotheses",
     "uvo_matcher_kernel_times", "uvo_last_error", "uvo_device_info",
 ]
 
@@ -286,6 +287,12 @@ def _load():
     lib.uvo_sim3solver_iterate.argtypes = [vp, vp, ci, ci, vp, vp]
     lib.uvo_sim3solver_find.argtypes = [vp, ci, vp, vp]
     lib.uvo_sim3solver_hypotheses.argtypes = [vp, ci, vp, vp, vp, vp, ci, vp]
+    lib.uvo_initializer_create.argtypes = [vp, ci, vp]
+    lib.uvo_initializer_destroy.argtypes = [vp]
+    lib.uvo_initializer_destroy.restype = None
+    lib.uvo_initializer_set_reference.argtypes = [vp, vp, ci, vp, cf, ci]
+    lib.uvo_initializer_initialize.argtypes = [vp, vp, ci, vp, vp, vp]
+    lib.uvo_initializer_hypotheses.argtypes = [vp, vp, vp, vp, ci, vp]
     lib.uvo_fuse.argtypes = [vp, vp, ci, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, ci, cf, vp, vp]
     lib.uvo_search_for_triangulation_batch.argtypes = [vp, vp, vp, ci, vp, vp, ci, vp]
     lib.uvo_search_for_triangulation_next.argtypes = [vp, ci, vp, ci, vp, vp]
@@ -1566,6 +1573,82 @@ class Sim3SolverSet:
         if rc:
             raise UvoError(rc, "uvo_sim3solver_hypotheses")
         return sub[:n.value].copy(), t12[:n.value].copy(), t21[:n.value].copy(), cnt[:n.value].copy()
+
+
+class InitializerResultC(ctypes.Structure):
+    """uvo_initializer_result."""
+    _fields_ = [("initialized", ctypes.c_int32), ("best", ctypes.c_int32), ("n_inliers", ctypes.c_int32), ("draws", ctypes.c_uint32),
+                ("deciding", ctypes.c_int32), ("n_good", ctypes.c_int32 * 4), ("parallax", ctypes.c_float * 4), ("score", ctypes.c_float),
+                ("R21", ctypes.c_float * 9), ("t21", ctypes.c_float * 3), ("F21", ctypes.c_float * 9), ("pad_", ctypes.c_int32),
+                ("inliers", ctypes.c_void_p), ("p3d", ctypes.c_void_p), ("triangulated", ctypes.c_void_p)]
+
+
+class InitializerResult:
+    """One Initialize call: initialized (its return value), best (the hypothesis kept, -1: none), n_inliers, draws, deciding (0..3, -1),
+    n_good int32[4], parallax float32[4], score (SF), R21 float32[3, 3], t21 float32[3], F21 float32[3, 3], inliers uint8[n2],
+    p3d float32[n2, 3] and triangulated uint8[n2], both indexed by the current frame's key."""
+
+    def __init__(self, c, inliers, p3d, triangulated):
+        self.initialized, self.best, self.n_inliers, self.draws, self.deciding = bool(c.initialized), c.best, c.n_inliers, c.draws, c.deciding
+        self.n_good, self.parallax, self.score = np.array(c.n_good, np.int32), np.array(c.parallax, np.float32), np.float32(c.score)
+        self.R21, self.t21 = np.array(c.R21, np.float32).reshape(3, 3), np.array(c.t21, np.float32)
+        self.F21 = np.array(c.F21, np.float32).reshape(3, 3)
+        self.inliers, self.p3d, self.triangulated = inliers, p3d, triangulated
+
+
+class Initializer:
+    """USLAM::Initializer for Tracking::Initialize (src/Tracking.cc:1340, :1582): the F path of Initialize as one device call on a KLT
+    handle.  `_api` / `_prefix` exist so that the tests' host build of the same source can be driven through this very class."""
+    _prefix = "uvo_initializer_"
+
+    def __init__(self, klt, max_keys, _api=None):
+        self._api = _api if _api is not None else lib
+        self._klt = klt   # the object launches in the handle's stream: keep it alive
+        self._h = ctypes.c_void_p()
+        rc = self._f("create")(klt._h if klt is not None else None, max_keys, ctypes.byref(self._h))
+        if rc:
+            raise UvoError(rc, "uvo_initializer_create")
+
+    def _f(self, name):
+        return getattr(self._api, self._prefix + name)
+
+    def close(self):
+        if getattr(self, "_h", None) and self._api is not None:
+            self._f("destroy")(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def set_reference(self, keys1, cam, sigma=1.0, iterations=200):
+        """Initializer(ReferenceFrame, sigma, iterations): keys1 float32[n1, 2] = mvKeysUn, cam a CameraModel or (fx, fy, cx, cy)."""
+        k1 = np.ascontiguousarray(keys1, np.float32).reshape(-1, 2)
+        c = cam if isinstance(cam, CameraModel) else CameraModel.make(*cam, [])
+        rc = self._f("set_reference")(self._h, _ptr(k1), len(k1), ctypes.addressof(c), float(sigma), int(iterations))
+        if rc:
+            raise UvoError(rc, "uvo_initializer_set_reference")
+
+    def initialize(self, keys2, matches12, rng):
+        """Initialize(CurrentFrame, vMatches12, ...): keys2 float32[n2, 2], matches12 int32[n2]; rng (GlibcRand) is advanced in place."""
+        k2 = np.ascontiguousarray(keys2, np.float32).reshape(-1, 2)
+        m = np.ascontiguousarray(matches12, np.int32).reshape(-1)
+        if len(m) != len(k2):
+            raise ValueError("keys2 and matches12 differ in length")
+        n = len(k2)
+        inl, p3d, tri = np.zeros(max(n, 1), np.uint8), np.zeros((max(n, 1), 3), np.float32), np.zeros(max(n, 1), np.uint8)
+        res = InitializerResultC()
+        res.inliers, res.p3d, res.triangulated = inl.ctypes.data, p3d.ctypes.data, tri.ctypes.data
+        rc = self._f("initialize")(self._h, _ptr(k2), n, _ptr(m), ctypes.addressof(rng), ctypes.byref(res))
+        if rc:
+            raise UvoError(rc, "uvo_initializer_initialize")
+        return InitializerResult(res, inl[:n], p3d[:n], tri[:n])
+
+    def hypotheses(self, cap=1024):
+        """Test tap: (sets int32[h, 8], F21i float32[h, 9], scores float32[h]) of the last initialize call."""
+        sub, F, sc, n = np.zeros((cap, 8), np.int32), np.zeros((cap, 9), np.float32), np.zeros(cap, np.float32), ctypes.c_int()
+        rc = self._f("hypotheses")(self._h, _ptr(sub), _ptr(F), _ptr(sc), cap, ctypes.byref(n))
+        if rc:
+            raise UvoError(rc, "uvo_initializer_hypotheses")
+        return sub[:n.value].copy(), F[:n.value].copy(), sc[:n.value].copy()
 
 
 class KltCfg(ctypes.Structure):
