@@ -14,6 +14,7 @@
 #pragma once
 #include "strip_plan.hpp"
 #include "pyr_tiles.hpp"
+#include "resize_rows.hpp"
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -135,6 +136,11 @@ void launch_pad_level0(hipStream_t s, const uint8_t* d_img, int w, int h, int64_
                        int64_t pyr_block, const LevelGeom& g0, int batch);
 void launch_resize_level(hipStream_t s, uint8_t* d_pyr, int64_t pyr_block, const LevelGeom& src, const LevelGeom& dst, const ResizeCol* d_ctab,
                          const ResizeRow* d_rtab, int fast_ok, int batch, Level0View l0, int ring);
+// the same level as a walk down row bands (pyramid.hip: k_resize_level_rows; schedule: resize_rows.hpp).  _applies: the level can take the form
+// (12-byte-window levels whose frames the 32-bit lane offsets cover) and, unless forced, the launch is large enough for it to pay
+bool resize_level_rows_applies(const LevelGeom& src, const LevelGeom& dst, int fast_ok, int batch, Level0View l0, int ring, int64_t pyr_block, bool forced);
+void launch_resize_level_rows(hipStream_t s, uint8_t* d_pyr, int64_t pyr_block, const LevelGeom& src, const LevelGeom& dst, const ResizeCol* d_ctab,
+                              const ResizeRow* d_rtab, int batch, Level0View l0, int ring);
 // a group of consecutive levels in one launch (pyramid.hip: k_pyr_tiles; plan: pyr_tiles.hpp)
 constexpr int kPyrTilesMaxLds = 160 * 1024;
 int prepare_pyr_tiles(uint32_t* max_lds);  // *max_lds: bytes of LDS a tile plan may use on the current device

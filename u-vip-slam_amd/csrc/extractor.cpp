@@ -243,10 +243,19 @@ int run_batch_device(uvo_extractor* h, int li, const Batch& b) {
         launch_pyr_tiles(s, L.d.pyr, g.pyr_block, G.d_plan, g, h->d_ctab, h->d_rtab, l0, G.first, G.last, G.tx * G.ty, G.lds, G.threads, G.rows, batch);
       }
     } else {
+      // large batches walk row bands (k_resize_level_rows: a source row is filtered once), level by level where the launch is large enough
+      const bool rows = h->pyr_form == UVO_PYR_FORM_ROWS || (h->pyr_form == UVO_PYR_FORM_AUTO && batch > kTilePyramidFrames);
       for (int l = 1; l < g.nlevels; ++l) {
-        ProfScope p(h, "k_resize_level");
-        launch_resize_level(s, L.d.pyr, g.pyr_block, g.lv[l - 1], g.lv[l], h->d_ctab + g.lv[l].xtab_off, h->d_rtab + g.lv[l].ytab_off, h->resize_fast[l],
-                            batch, l == 1 ? l0 : no_l0, h->pyr_ring);
+        const Level0View v = l == 1 ? l0 : no_l0;
+        const ResizeCol* ct = h->d_ctab + g.lv[l].xtab_off;
+        const ResizeRow* rt = h->d_rtab + g.lv[l].ytab_off;
+        if (rows && resize_level_rows_applies(g.lv[l - 1], g.lv[l], h->resize_fast[l], batch, v, h->pyr_ring, g.pyr_block, h->pyr_form == UVO_PYR_FORM_ROWS)) {
+          ProfScope p(h, "k_resize_level_rows");
+          launch_resize_level_rows(s, L.d.pyr, g.pyr_block, g.lv[l - 1], g.lv[l], ct, rt, batch, v, h->pyr_ring);
+        } else {
+          ProfScope p(h, "k_resize_level");
+          launch_resize_level(s, L.d.pyr, g.pyr_block, g.lv[l - 1], g.lv[l], ct, rt, h->resize_fast[l], batch, v, h->pyr_ring);
+        }
       }
     }
   }
@@ -577,7 +586,7 @@ int uvo_extractor_tune(uvo_extractor* h, int knob, int value) {
       return UVO_OK;
     }
     case UVO_TUNE_PYR_FORM:
-      if (value < UVO_PYR_FORM_AUTO || value > UVO_PYR_FORM_TILES) return fail(UVO_E_BADARG, "UVO_TUNE_PYR_FORM takes UVO_PYR_FORM_AUTO / _LEVELS / _TILES");
+      if (value < UVO_PYR_FORM_AUTO || value > UVO_PYR_FORM_ROWS) return fail(UVO_E_BADARG, "UVO_TUNE_PYR_FORM takes UVO_PYR_FORM_AUTO / _LEVELS / _TILES / _ROWS");
       h->pyr_form = value;
       return UVO_OK;
     case UVO_TUNE_PYR_TILE_GROUP: {

@@ -250,6 +250,204 @@ void launch_resize_level(hipStream_t s, uint8_t* d_pyr, int64_t pyr_block, const
   }
 }
 
+// =====================================================================================================================
+// k_resize_level_rows: the per-level resize of a batch as a walk down row bands (schedule: resize_rows.hpp).  k_resize_level's arithmetic and
+// tables; what differs is who computes what.  A wavefront owns 64 consecutive entries of the launch's flattened (frame, dword column) space --
+// no lane idles on rows of 51 - 136 dwords -- and UVO_RESIZE_BAND consecutive output rows.  A lane keeps the horizontal pass of two source
+// rows in registers (two register sets that swap roles from row to row).  The upper source row of an output row is loaded and filtered only
+// when the lane does not hold it; the lower one always (rows_walk says why).  At scale 1.2 and ring 4 that is 1.26 source rows filtered per
+// output row where k_resize_level filters 2 (tests/emu/resize_rows_emu.cpp prints the figure per level).  Loads are more than that: the
+// look-ahead behind a band's last row is issued and dropped (UVO_RESIZE_AHEAD rows of 1.2 source rows per 16-row band), so a lane loads
+// (1.26 + 3 x 1.2 / 16) x 3 = 4.5 dwords per output dword against k_resize_level's 6 -- not the 3.6 a walk without look-ahead would have.
+// Counters (profiles/r13_resize_rows_counters.json, level 1): vector instructions 19.3 M -> 14.2 M wave-instructions, fetched bytes 1.25 x
+// k_resize_level's: the band's first source row and the look-ahead rows are the neighbouring bands' rows, fetched by both at the same time.
+// Everything about a row is wave-uniform.  The band's row-table entries are fetched with ONE vector load (lane j holds row j's) and read
+// back with v_readlane: a scalar load per row would put a wait for the scalar cache into every row of the walk.  The decision which rows to
+// filter is scalar (resize_rows_step); a row's address is a scalar offset added to the lane's constant address.
+struct ResizeRowsArgs {
+  const uint8_t* src;  // ROI pixel (0, 0) of the source level of the launch's first frame (the padded plane's, or the caller's image in place)
+  uint8_t* dst;        // padded plane of the launch's first frame
+  uint32_t src_frame, dst_frame;  // frame strides in bytes (frames * stride < 2^32: resize_rows_max_frames)
+  int src_pitch, dst_pitch, sh;
+  int guard;           // the source is the caller's image: no load may pass guard_lim
+  uint32_t guard_lim;  // offset from a frame's ROI origin of the frame's last whole dword
+  const ResizeCol* ctab;
+  const ResizeRow* rtab;
+  int rtab_last;  // last entry of the (padded) row table
+  ResizeRowsRegion r;
+  uint32_t nwx_magic, nbands_magic, entries, nitems, per_xcd;
+};
+
+static_assert(UVO_RESIZE_AHEAD >= 1 && UVO_RESIZE_BAND >= 2 && UVO_RESIZE_BAND + UVO_RESIZE_AHEAD <= 64,
+              "lane j of a wavefront holds the table entry of the band's row j, lanes n .. n + UVO_RESIZE_AHEAD - 1 the look-ahead's");
+
+// the three window dwords of source row sy at the lane's columns.  GUARD (in place, a band that reaches the frame's last source row): a
+// window dword behind the frame's last byte is not loaded -- the frame's last dword is, whose bytes carry no weight there (k_resize_level)
+template <bool GUARD>
+__device__ __forceinline__ void rows_load(const uint8_t* __restrict__ S, int sy, int pitch, uint32_t vsrc, uint32_t glim, uint32_t (&u)[3]) {
+  const uint32_t ro = (uint32_t)sy * (uint32_t)pitch;  // scalar
+  if (!GUARD) {
+    const uint8_t* p = S + ro;  // scalar base + the lane's 32-bit offset: no vector address arithmetic
+#pragma unroll
+    for (int k = 0; k < 3; ++k) u[k] = *reinterpret_cast<const uint32_t*>(p + (uint64_t)vsrc + 4 * k);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) u[k] = *reinterpret_cast<const uint32_t*>(S + (uint64_t)(vsrc + min(ro + 4u * k, glim)));
+  }
+}
+__device__ __forceinline__ void rows_hfilter(const uint32_t (&u)[3], uint32_t sel, const uint32_t (&a0)[4], const uint32_t (&a1)[4], uint32_t (&q)[4]) {
+  const uint32_t L = __builtin_amdgcn_perm(u[1], u[0], sel);
+  const uint32_t R = __builtin_amdgcn_perm(__builtin_amdgcn_alignbyte(u[2], u[1], 1), __builtin_amdgcn_alignbyte(u[1], u[0], 1), sel);
+  q[0] = hrow<0>(L, R, a0[0], a1[0]), q[1] = hrow<1>(L, R, a0[1], a1[1]), q[2] = hrow<2>(L, R, a0[2], a1[2]), q[3] = hrow<3>(L, R, a0[3], a1[3]);
+}
+__device__ __forceinline__ uint32_t rows_vfilter(const uint32_t (&q0)[4], const uint32_t (&q1)[4], uint32_t b0s, uint32_t b1s) {
+  return vrow(q0[0], q1[0], b0s, b1s) | vrow(q0[1], q1[1], b0s, b1s) << 8 | vrow(q0[2], q1[2], b0s, b1s) << 16 | vrow(q0[3], q1[3], b0s, b1s) << 24;
+}
+
+struct RowsLane {  // what a lane keeps for the whole band
+  uint32_t a0[4], a1[4], sel;
+  uint32_t vsrc, glim, vdst;  // 32-bit offsets from the launch's source / destination base; GUARD: the lane's last loadable offset in a row
+  uint32_t tsy, tb;           // lane j: (sy0 | sy1 << 16) and (b0 | b1 << 16) of the band's row j
+};
+
+// The walk.  Output row J of the band is computed from ring entry J % R of the raw window dwords (R = UVO_RESIZE_AHEAD + 1) while the loads of
+// rows J + 1 .. J + UVO_RESIZE_AHEAD are in flight; the body is unrolled over lcm(2, R) rows, so that ring entries and the slots' roles (row
+// parity) are constants of the code and nothing is moved.  The lower source row is loaded and filtered always: it is the one a monotone walk
+// misses (it is held only where the table clamps or runs backwards, and filtering it again gives the same words), and a load whose use sits
+// behind a branch makes the compiler drain every load in flight before it may reuse the registers.  The upper row (missed on a step of two
+// source rows, one output row in five at scale 1.2) takes the branch.  The loads behind the band's last row (clamped into the table, so
+// always inside the plane) are issued and dropped: they are the first rows of the band below, which runs next to this one.
+template <bool GUARD>
+__device__ __forceinline__ void rows_walk(const ResizeRowsArgs& A, const RowsLane& T, int py0, int n) {
+  constexpr int AH = UVO_RESIZE_AHEAD, R = AH + 1, U = R % 2 ? 2 * R : R;
+  const uint8_t* __restrict__ S = A.src;
+  uint8_t* drow = A.dst + (int64_t)py0 * A.dst_pitch;  // scalar: advances by one row per output row
+  const int spitch = A.src_pitch;
+  uint32_t slot[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+  ResizeRowsState st{{-1, -1}};
+  uint32_t ua[R][3], ub[R][3];  // raw window dwords of the upper / lower source row
+  ResizeRowsStep stp[R];
+#pragma unroll
+  for (int k = 0; k < AH; ++k) {
+    const uint32_t e = (uint32_t)__builtin_amdgcn_readlane((int)T.tsy, k);
+    stp[k] = resize_rows_step(st, k & 1, (int)(e & 0xffffu), (int)(e >> 16));
+    if (stp[k].eval0) rows_load<GUARD>(S, (int)(e & 0xffffu), spitch, T.vsrc, T.glim, ua[k]);
+    rows_load<GUARD>(S, (int)(e >> 16), spitch, T.vsrc, T.glim, ub[k]);
+  }
+  for (int j = 0;; j += U) {
+#pragma unroll
+    for (int k = 0; k < U; ++k) {
+      const int c = k % R, nx = (k + AH) % R, p = k & 1;
+      const uint32_t e = (uint32_t)__builtin_amdgcn_readlane((int)T.tsy, j + k + AH);
+      stp[nx] = resize_rows_step(st, (k + AH) & 1, (int)(e & 0xffffu), (int)(e >> 16));
+      if (stp[nx].eval0) rows_load<GUARD>(S, (int)(e & 0xffffu), spitch, T.vsrc, T.glim, ua[nx]);
+      rows_load<GUARD>(S, (int)(e >> 16), spitch, T.vsrc, T.glim, ub[nx]);
+      const uint32_t bw = (uint32_t)__builtin_amdgcn_readlane((int)T.tb, j + k);
+      const uint32_t b0s = (bw & 0xffffu) << 8, b1s = (bw >> 16) << 8;
+      if (stp[c].eval0) rows_hfilter(ua[c], T.sel, T.a0, T.a1, slot[p]);
+      rows_hfilter(ub[c], T.sel, T.a0, T.a1, slot[p ^ 1]);
+      *reinterpret_cast<uint32_t*>(drow + (uint64_t)T.vdst) = rows_vfilter(slot[p], slot[p ^ 1], b0s, b1s);
+      drow += A.dst_pitch;
+      if (j + k + 1 >= n) return;  // (n >= 1; the way out leaves the loop at once: a path that rejoined it would carry its unused loads along)
+    }
+  }
+}
+
+#ifndef UVO_OCC_RESIZE_ROWS
+#define UVO_OCC_RESIZE_ROWS 8
+#endif
+__global__ __launch_bounds__(256, UVO_OCC_RESIZE_ROWS) void k_resize_level_rows(ResizeRowsArgs A) {
+  // workgroup b runs on XCD b & 7 and takes item (b & 7) * per_xcd + (b >> 3) of the list of workgroups; the list is chunk-major, so an XCD
+  // walks whole frames and the bands of one column chunk -- which share their boundary source row -- run next to each other
+  const uint32_t vb = (blockIdx.x & 7u) * A.per_xcd + (blockIdx.x >> 3);
+  const uint32_t item = vb * 4u + (uint32_t)wave_in_block();
+  if (item >= A.nitems) return;
+  const uint32_t chunk = __umulhi(item, A.nbands_magic);  // item / nbands (exact: resize_rows_max_frames)
+  const int band = (int)(item - chunk * (uint32_t)A.r.nbands);
+  int py0, n;
+  resize_rows_band(A.r, band, &py0, &n);
+  const uint32_t lane = threadIdx.x & 63u;
+  RowsLane T;
+  const uint32_t ent = chunk * 64u + lane;
+  // (a lane past the end computes and stores the last entry again -- the same word to the same address: a store under a lane mask would sit
+  // behind a branch, and the compiler then waits for the previous row's store before it touches the next row's loads)
+  const uint32_t en = min(ent, A.entries - 1u);
+  const uint32_t f = __umulhi(en, A.nwx_magic);         // en / nwx
+  const int wx = (int)(en - f * (uint32_t)A.r.nwx) + A.r.wx0;
+  const uint4 c01 = reinterpret_cast<const uint4*>(A.ctab)[wx * 2], c23 = reinterpret_cast<const uint4*>(A.ctab)[wx * 2 + 1];
+  const uint32_t cw[8] = {c01.x, c01.y, c01.z, c01.w, c23.x, c23.y, c23.z, c23.w};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) T.a0[i] = cw[2 * i] >> 16, T.a1[i] = cw[2 * i + 1] & 0xffffu;
+  const uint32_t base = cw[1] >> 16;
+  T.sel = (cw[3] >> 16) | (cw[5] & 0xffff0000u);
+  T.vsrc = f * A.src_frame + base;
+  T.vdst = f * A.dst_frame + (uint32_t)wx * 4u;
+  T.glim = A.guard_lim - base;
+  // lane j: the table entry of the band's row j; lanes n ..: the look-ahead behind the band's last row (clamped into the table)
+  const uint2 te = reinterpret_cast<const uint2*>(A.rtab)[min(py0 + (int)lane, A.rtab_last)];
+  T.tsy = te.x, T.tb = te.y;
+  // in place, a band that reaches the frame's last source row (its look-ahead included) keeps every load inside the frame
+  const bool guard = A.guard && __ballot((int)lane < n + UVO_RESIZE_AHEAD && (int)(te.x >> 16) >= A.sh - 1) != 0ull;
+  if (guard) rows_walk<true>(A, T, py0, n);
+  else rows_walk<false>(A, T, py0, n);
+}
+
+#ifndef UVO_RESIZE_ROWS_MIN_ITEMS
+// UVO_PYR_FORM_AUTO: launches of fewer work items (wavefronts) keep k_resize_level.  A level is a ramp, a walk and a tail: with a couple of
+// thousand wavefronts on 256 CUs the walk's 16 rows in sequence take as long as k_resize_level's short-lived wavefronts.  640 x 512, 257
+// frames, ring 4 (15 316, 10 442, 7 258, 5 152, 3 780, 2 700 and 1 890 items on levels 1 - 7), rocprofv3 at depth 1: levels 1 - 5 are 9.8, 2.1, 1.5,
+// 0.4 and 0.8 us shorter as rows, levels 6 and 7 0.3 and 0.4 us longer; k_resize_level behind a level that the rows form wrote is 1.4 us
+// longer than behind its own.  bench.py, seven runs a side on one box: thresholds 0 / 2048 / 3072 give medians of 319 200 / 318 900 /
+// 317 100 frames/s against the parent's 313 700 -- 0 and 2048 are the same within the runs' spread.  2048 is kept: it gives the benchmark's
+// levels 1 - 6 to the rows form and leaves the small launches of batches of 9 - 40 frames, which nobody measured, where they were
+// (profiles/r13_resize_rows_ab.txt, profiles/LOG.md r13).
+#define UVO_RESIZE_ROWS_MIN_ITEMS 2048
+#endif
+
+// frames per launch of the rows form for this level (0: the level keeps k_resize_level -- byte-gather levels, strides the 32-bit lane offsets do
+// not cover)
+static int64_t resize_rows_frames(const LevelGeom& src, const LevelGeom& dst, int fast_ok, Level0View l0, int ring, int64_t pyr_block) {
+  if (!fast_ok) return 0;
+  const ResizeRowsRegion r = resize_rows_region(dst.w, dst.h, dst.pitch, ring);
+  int64_t frame_bytes = pyr_block;
+  if (l0.vbase) {
+    if (l0.frame_stride < (int64_t)(src.h - 1) * l0.pitch + src.w) return 0;  // (frames that overlap or run backwards)
+    frame_bytes = std::max<int64_t>(frame_bytes, l0.frame_stride);
+  }
+  return resize_rows_max_frames(r.nwx, r.nbands, frame_bytes);
+}
+
+bool resize_level_rows_applies(const LevelGeom& src, const LevelGeom& dst, int fast_ok, int batch, Level0View l0, int ring, int64_t pyr_block, bool forced) {
+  if (resize_rows_frames(src, dst, fast_ok, l0, ring, pyr_block) < 1) return false;
+  if (forced) return true;
+  const ResizeRowsRegion r = resize_rows_region(dst.w, dst.h, dst.pitch, ring);
+  return ((int64_t)batch * r.nwx + 63) / 64 * r.nbands >= UVO_RESIZE_ROWS_MIN_ITEMS;
+}
+
+void launch_resize_level_rows(hipStream_t s, uint8_t* d_pyr, int64_t pyr_block, const LevelGeom& src, const LevelGeom& dst, const ResizeCol* d_ctab,
+                              const ResizeRow* d_rtab, int batch, Level0View l0, int ring) {
+  const int max_frames = (int)resize_rows_frames(src, dst, 1, l0, ring, pyr_block);  // >= 1: resize_level_rows_applies
+  ResizeRowsArgs A;
+  memset(&A, 0, sizeof(A));
+  A.r = resize_rows_region(dst.w, dst.h, dst.pitch, ring);
+  A.src_pitch = l0.vbase ? l0.pitch : src.pitch, A.dst_pitch = dst.pitch, A.sh = src.h;
+  A.src_frame = (uint32_t)(l0.vbase ? l0.frame_stride : pyr_block), A.dst_frame = (uint32_t)pyr_block;
+  A.guard = l0.vbase != nullptr;
+  A.guard_lim = (uint32_t)((int64_t)(src.h - 1) * A.src_pitch + src.w - 4);  // (rows and the frame's end are dword-aligned in place)
+  A.ctab = d_ctab, A.rtab = d_rtab, A.rtab_last = ((dst.ph + 3) & ~3) - 1;
+  A.nwx_magic = (uint32_t)((0x100000000ull + (uint32_t)A.r.nwx - 1) / (uint32_t)A.r.nwx);
+  A.nbands_magic = (uint32_t)((0x100000000ull + (uint32_t)A.r.nbands - 1) / (uint32_t)A.r.nbands);
+  for (int f0 = 0; f0 < batch; f0 += max_frames) {
+    const int nb = std::min(batch - f0, max_frames);
+    A.src = l0.vbase ? l0.vbase + (int64_t)f0 * l0.frame_stride + (int64_t)kPad * l0.pitch + kPad
+                     : d_pyr + (int64_t)f0 * pyr_block + src.plane_off + (int64_t)kPad * src.pitch + kPad;
+    A.dst = d_pyr + (int64_t)f0 * pyr_block + dst.plane_off;
+    A.entries = (uint32_t)nb * (uint32_t)A.r.nwx;
+    A.nitems = (A.entries + 63u) / 64u * (uint32_t)A.r.nbands;
+    A.per_xcd = ((A.nitems + 3u) / 4u + 7u) / 8u;
+    hipLaunchKernelGGL(k_resize_level_rows, dim3(8 * A.per_xcd), dim3(256), 0, s, A);
+  }
+}
 
 // =====================================================================================================================
 // k_pyr_tiles: a GROUP of consecutive pyramid levels in one launch (plan: pyr_tiles.hpp).  Workgroup = (frame, tile); it walks the group's

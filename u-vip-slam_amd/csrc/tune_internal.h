@@ -7,10 +7,12 @@
 #define UVO_TUNE_FUSE_BLUR_TREE 10 /* 1 (default): DistributeOctTree and GaussianBlur share one launch when the batch is large enough for the
                                      256-thread quad-tree form (neither reads what the other writes); 0: two launches */
 #define UVO_TUNE_PYR_FORM 13        /* launch shape of ComputePyramid (src/ORBextractor.cc:963-1004); the planes are the same in every form */
-#define UVO_PYR_FORM_AUTO 0              /* (default) up to 8 frames one k_pyr_tiles launch, larger batches one launch per level; the per-level launches also
+#define UVO_PYR_FORM_AUTO 0              /* (default) up to 8 frames one k_pyr_tiles launch, larger batches one launch per level (k_resize_level_rows where the
+                                            launch is large enough for it, k_resize_level on the others); the per-level launches also
                                             where a geometry has no tile plan (scale factors above ~1.33, UVO_TUNE_PYR_RING != 4) */
 #define UVO_PYR_FORM_LEVELS 1            /* one launch per level (k_resize_level) */
 #define UVO_PYR_FORM_TILES 2             /* k_pyr_tiles for every batch size */
+#define UVO_PYR_FORM_ROWS 3              /* one launch per level, every level that can as a walk down row bands (k_resize_level_rows), whatever the batch size */
 #define UVO_TUNE_PYR_TILE_GROUP 14  /* forces the level groups of k_pyr_tiles: one call per group, value = first level << 16 | tx << 8 | ty
                                        (| 1 << 24: 1024-thread workgroups; | 1 << 25: 1024 threads, one output row per work item), first level 1 starts a new
                                        list; 0: back to the defaults */
