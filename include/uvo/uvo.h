@@ -418,7 +418,7 @@ typedef struct uvo_match_rule {
   int32_t rule;              /* UVO_RULE_* */
   int32_t max_dist;          /* TH_HIGH (100), TH_LOW (50) or the caller's ORBdist */
   float nn_ratio;            /* mfNNratio */
-  int32_t exclusive;         /* 1: a target accepted by an earlier query is skipped by later ones */
+  int32_t exclusive;         /* 1: a target accepted by an earlier query is skipped by later ones (blocked targets are skipped either way) */
   int32_t check_orientation; /* mbCheckOrientation: rotation histogram + ComputeThreeMaxima (:1748-1789) */
 } uvo_match_rule;
 /* ORBmatcher::CheckDistEpipolarLine (:136-153): l = x1' F12; dsqr = (l . x2)^2 / (a^2+b^2) < 3.84 * sigma2[octave2] */

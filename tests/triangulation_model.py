@@ -296,6 +296,40 @@ def match_list_scene(seed, n, noise=0.5, parallax_deg=5.0, wrong_share=0.15):
     return dict(cam1=cam1, cam2=cam2, kp1=kp1, kp2=kp2, depth=depth, ratio_factor=ratio_factor(cam1), Xw=Xw)
 
 
+def pile_scene(n_a=1030, n_b=120, k=60, extra2=0):
+    """The pile of tests/resolve_model.py as a CreateNewMapPoints scene: two vocabulary nodes, each one all-to-all group.  Node 3 holds
+    features 0..n_a-1 of key frame 1 and key points 0..k-1 of key frame 2, node 10 the n_b features behind them and key points k..2k-1.
+    Every feature of key frame 1 has the zero descriptor, key point j of a node its first j bits set: distance j from every feature.
+    The cameras differ by a sideways translation and every key point lies on the row y = cy, so CheckDistEpipolarLine passes for every
+    pair and the acceptance loop of SearchForTriangulation is left to its order alone: the i-th free feature of a node ends on the
+    node's key point i while i <= TH_LOW.  Key point j of a node is the true observation of the world point of the node's feature j, so
+    the first pair's matches triangulate; two pairs, the second one sees the map points the first one made.  extra2 key points of a node
+    that key frame 1 does not have stand in FRONT of key frame 2's others: never candidates, they only make the frame large."""
+    import resolve_model as rm
+    I = np.eye(3)
+    cam1, cams2 = Camera(I, [0, 0, 0]), [Camera(I, [-1.0, 0, 0]), Camera(I, [-0.7, 0, 0])]
+    n1 = n_a + n_b
+    u = 40.0 + (np.arange(n1) * 37 % 660).astype(np.float64)
+    z = 4.0 + (np.arange(n1) * 13 % 80) / 10.0
+    Xw = np.stack([(u - float(cam1.cx)) / float(cam1.fx) * z, np.zeros(n1), z], 1)
+    kp1 = np.zeros(n1, KP)
+    kp1["x"], kp1["y"], kp1["size"] = u, float(cam1.cy), 31.0
+    desc1, pile_t = rm.pile_descriptors(n1, k)
+    seen = np.r_[np.arange(k), n_a + np.arange(k)]                       # the features whose world points key frame 2 observes
+    pairs = []
+    for cam2 in cams2:
+        pu, _, _ = cam2.project(Xw[seen])
+        kp2 = np.zeros(extra2 + 2 * k, KP)
+        kp2["x"], kp2["y"], kp2["size"] = np.r_[np.arange(extra2) % 700, pu], float(cam2.cy), 31.0
+        groups = {3: list(range(extra2, extra2 + k)), 10: list(range(extra2 + k, extra2 + 2 * k))}
+        if extra2:
+            groups[99] = list(range(extra2))
+        pairs.append(dict(groups=groups, kp=kp2, desc=np.concatenate([np.zeros((extra2, 32), np.uint8), pile_t, pile_t]),
+                          has_mp=np.zeros(extra2 + 2 * k, np.uint8), F12=compute_f12(cam1, cam2), sigma2=cam2.sigma2))
+    return dict(cam1=cam1, cams2=cams2, kp1=kp1, desc1=desc1, groups1={3: list(range(n_a)), 10: list(range(n_a, n1))},
+                has_mp1=np.zeros(n1, np.uint8), pairs=pairs, depth=8.0, ratio_factor=ratio_factor(cam1))
+
+
 # the committed match-list scenes of the GPU grid: (seed, n, noise px, parallax degrees)
 GRID_SCENES = [(200 + 10 * i + j, n, noise, par) for i, n in enumerate((0, 1, 63, 64, 65, 1000))
                for j, (noise, par) in enumerate(((0.0, 5.0), (0.5, 2.0), (1.5, 10.0)))]

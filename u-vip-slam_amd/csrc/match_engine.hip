@@ -181,13 +181,15 @@ __device__ __forceinline__ int rule_choice(const MatchRule& R, int i, const int3
                                            int* dist) {
   const int b = cand_start[i], e = cand_start[i + 1];
   *dist = -1;
+  // a target is unavailable when owner[t] < lim: taken by an earlier query (exclusive), or blocked from the start (owner -1, always)
+  const int lim = R.exclusive ? i : 0;
   if (R.rule == UVO_RULE_TRIANGULATION) {
     // :893-935 -- free candidates with d <= TH_LOW, sorted by (d, idx2); walk while d <= round(2*best); first that passes
     // the epipolar test
     int best = 0x7fffffff;
     for (int c = b; c < e; ++c) {
       const uint32_t v = cand[c];
-      if (R.exclusive && owner[v & 0xffffu] < i) continue;
+      if (owner[v & 0xffffu] < lim) continue;
       const int d = (int)((v >> 16) & 0x1ffu);
       if (d > R.max_dist) continue;
       best = d < best ? d : best;
@@ -198,7 +200,7 @@ __device__ __forceinline__ int rule_choice(const MatchRule& R, int i, const int3
     for (int c = b; c < e; ++c) {
       const uint32_t v = cand[c];
       if (!(v >> 31)) continue;
-      if (R.exclusive && owner[v & 0xffffu] < i) continue;
+      if (owner[v & 0xffffu] < lim) continue;
       const int d = (int)((v >> 16) & 0x1ffu);
       if (d > R.max_dist || d > dist_th) continue;
       const uint32_t key = ((uint32_t)d << 16) | (v & 0xffffu);
@@ -217,13 +219,13 @@ __device__ __forceinline__ int rule_choice(const MatchRule& R, int i, const int3
 #pragma unroll
     for (int k = 0; k < 8; ++k) vv[k] = c0 + k < e ? cand[c0 + k] : 0u;
 #pragma unroll
-    for (int k = 0; k < 8; ++k) ow[k] = (R.exclusive && c0 + k < e) ? owner[vv[k] & 0xffffu] : 0x7fffffff;
+    for (int k = 0; k < 8; ++k) ow[k] = c0 + k < e ? owner[vv[k] & 0xffffu] : 0x7fffffff;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       if (c0 + k >= e) break;
       const uint32_t v = vv[k];
       const int idx = (int)(v & 0xffffu);
-      if (R.exclusive && ow[k] < i) continue;  // taken before this query's turn (or blocked from the start)
+      if (ow[k] < lim) continue;  // taken before this query's turn, or blocked from the start
       const int d = (int)((v >> 16) & 0x1ffu), oct = (int)((v >> 25) & 63u);
       if (d < bestDist) {
         bestDist2 = bestDist;

@@ -9,7 +9,7 @@
 //                  write at :119).  It is solved exactly as a fixed point: owner[k] = lowest-index map point whose
 //                  accepted choice is keypoint k; map point i may not use k when owner[k] < i.  Map point 0 is final
 //                  after one sweep, map point i after at most i+1, so the iteration ends in the sequential result;
-//                  in practice dependency chains are 2-4 deep.
+//                  how deep the chains go, and the scenes that drive them to one sweep per map point: DESIGN.md section 3.1.
 #include "common.hpp"
 
 namespace uvo {
