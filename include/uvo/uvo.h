@@ -387,6 +387,10 @@ int uvo_distinctive_descriptors(uvo_matcher* m, const uint8_t* desc, const int32
  *   assigned[n] : in/out, index of the map point held by keypoint i or -1 (reference: F.mvpMapPoints[i] != NULL)
  *   th, nnratio : call-site values (src/Tracking.cc:2222-2228);  scale_factors[nlevels] = F.mvScaleFactors
  * The greedy, order-dependent assignment of the reference is reproduced exactly.
+ * Window: radius (view_cos > 0.998 as a double ? 2.5f : 4.0f), times th when th != 1, times scale_factors[level], in float in that
+ * order; levels [level - 1, level]; grid and non-finite input as stated at uvo_match_windows: a key point with a NaN or infinite
+ * coordinate is never assigned, a map point whose proj_x, proj_y or radius (a NaN or infinite view_cos gives 4.0f; th and the scale
+ * factor enter the radius) is not finite matches nothing.
  */
 int uvo_search_by_projection(uvo_matcher* m, const uvo_keypoint* kp, int n, const uint8_t* desc, int min_x, int min_y, int max_x, int max_y,
                              int32_t* assigned, int nmp, const float* proj_x, const float* proj_y, const int32_t* level,
@@ -440,6 +444,24 @@ typedef struct uvo_epipolar {
  *                 (-1,-1 = no filter; equal = that level only), qvalid (0 = query skipped), qdesc, qangle (read only
  *                 when rule->check_orientation; the target angle is kp[].angle)
  *   match[nq]   : target index or -1;  dist[nq] : its distance or -1;  *n_matches : number of matches
+ * The list of a query is the reference's, element for element and in its order (ascending cell column, then cell row, then key-point
+ * index), held to a brute-force model in tests/test_gpu_windows.py:
+ *   grid     : cell = round() -- half away from zero -- of the float product (kp.x - min_x) * (64.0f / (max_x - min_x)), likewise y
+ *              with 48; a key point whose cell lies outside 0..63 x 0..47 is in no cell and in no list (the half cell at the right and
+ *              bottom edge rounds to 64 / 48; anything below -0.5, and -0.5 itself, rounds to -1 or less)
+ *   window   : columns max(0, floor((qx - min_x - qr) * inv_w)) .. min(63, ceil((qx - min_x + qr) * inv_w)), rows likewise; a window
+ *              wholly outside the grid is empty; inside it a key point is taken when !(|kp.x - qx| > qr) && !(|kp.y - qy| > qr): a
+ *              key point exactly at distance qr is in, qr = 0 finds a key point at the centre itself, a negative qr finds nothing
+ *   levels   : (-1, -1) no filter; qmin_level == qmax_level that level only; otherwise the range, so (-1, 0) is level 0 and below and
+ *              qmin_level > qmax_level is empty
+ *   not finite : a key point with a NaN or infinite x or y is in no cell; a query whose qx, qy or qr is NaN or infinite has an empty
+ *              list.  This is the reference's behaviour as built for x86, where such a float converts to INT_MIN (the key point fails
+ *              PosInGrid, the query returns at `nMaxCellX < 0`); the device's own conversion -- NaN to 0, infinities saturating --
+ *              is not relied on.
+ * The comparison holds for finite input whose cell expressions fit an int: |(qx - min_x +- qr) * inv_w| and the y counterpart below
+ * 2^31.  Beyond that (a finite radius of about 2^31 cells and more) the reference's answer rests on x86's out-of-range conversion; that
+ * case is outside this contract and untested.  Every entry point that builds the grid (this one, uvo_search_by_projection,
+ * uvo_search_by_projection_kf, uvo_fuse, uvo_fuse_batch, the Sim3 searches) shares the rule.
  */
 int uvo_match_windows(uvo_matcher* m, const uvo_keypoint* kp, int n, const uint8_t* desc, const uint8_t* blocked, int min_x, int min_y,
                       int max_x, int max_y, int nq, const float* qx, const float* qy, const float* qr, const int32_t* qmin_level,

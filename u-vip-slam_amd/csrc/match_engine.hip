@@ -65,7 +65,8 @@ __global__ __launch_bounds__(256) void k_win_cand(WinFrame F, WinQuery Q, const 
     y0 = max(0, y0);
     int y1 = (int)ceilf((y - (float)F.min_y + r) * F.inv_h);
     y1 = min(GR_ROWS - 1, y1);
-    if (x0 < GR_COLS && x1 >= 0 && y0 < GR_ROWS && y1 >= 0) {
+    // a centre or radius that is not finite finds nothing, as in the reference (see sbp_window in search.hip)
+    if (isfinite(x) && isfinite(y) && isfinite(r) && x0 < GR_COLS && x1 >= 0 && y0 < GR_ROWS && y1 >= 0) {
       const int o = FILL ? cand_start[i] : 0;
       uint4 q0 = make_uint4(0, 0, 0, 0), q1 = q0;
       if (FILL) {
@@ -754,7 +755,7 @@ __global__ __launch_bounds__(256) void k_fuse_walk(WinFrame F, int nmp, const ui
     y0 = max(0, y0);
     int y1 = (int)ceilf((y - (float)F.min_y + r) * F.inv_h);
     y1 = min(GR_ROWS - 1, y1);
-    if (x0 < GR_COLS && x1 >= 0 && y0 < GR_ROWS && y1 >= 0) {
+    if (isfinite(x) && isfinite(y) && isfinite(r) && x0 < GR_COLS && x1 >= 0 && y0 < GR_ROWS && y1 >= 0) {  // not finite: nothing, as k_win_cand
       const uint4* QD = reinterpret_cast<const uint4*>(mp_desc + (int64_t)i * 32);
       const uint4 q0 = QD[0], q1 = QD[1];
       for (int ix = x0; ix <= x1; ++ix) {

@@ -43,10 +43,12 @@ __global__ __launch_bounds__(GB_THREADS) void k_grid_build(SbpFrame F, int32_t* 
   for (int c = tid; c < NC; c += GB_THREADS) s_cnt[c] = 0, s_cur[c] = 0;
   __syncthreads();
   for (int i = tid; i < F.n; i += GB_THREADS) {
-    const int px = (int)roundf((F.kp[i].x - (float)F.min_x) * F.inv_w);
-    const int py = (int)roundf((F.kp[i].y - (float)F.min_y) * F.inv_h);
+    const float fx = (F.kp[i].x - (float)F.min_x) * F.inv_w, fy = (F.kp[i].y - (float)F.min_y) * F.inv_h;
+    const int px = (int)roundf(fx), py = (int)roundf(fy);
     int c = -1;
-    if (px >= 0 && px < GR_COLS && py >= 0 && py < GR_ROWS) {
+    // a key point with a NaN coordinate is in no cell: the reference's conversion gives INT_MIN for it, the device's gives 0
+    // (infinities saturate to INT_MAX / INT_MIN and leave the grid on their own)
+    if (fx == fx && fy == fy && px >= 0 && px < GR_COLS && py >= 0 && py < GR_ROWS) {
       c = px * GR_ROWS + py;
       atomicAdd(&s_cnt[c], 1);
     }
@@ -119,8 +121,11 @@ struct SbpMap {
   int n;
 };
 
-// window of GetFeaturesInArea (:364-382); returns false when the query leaves the grid
+// window of GetFeaturesInArea (:364-382); returns false when the query leaves the grid.  A centre or radius that is not finite finds
+// nothing: in the reference every such conversion gives INT_MIN and the test of nMaxCellX returns; here (int)NaN is 0 and infinities
+// saturate, which would walk cell (0, 0) or the whole grid with distance tests that NaN always passes.
 __device__ __forceinline__ bool sbp_window(const SbpFrame& F, float x, float y, float r, int& x0, int& x1, int& y0, int& y1) {
+  if (!(isfinite(x) && isfinite(y) && isfinite(r))) return false;
   x0 = (int)floorf((x - (float)F.min_x - r) * F.inv_w);
   x0 = max(0, x0);
   if (x0 >= GR_COLS) return false;
