@@ -553,7 +553,9 @@ __global__ __launch_bounds__(256) void k_project(int mode, ProjCam C, int n, con
     }
     if (mode == UVO_PROJECT_FRUSTUM) {
       const float ratio = max_raw[i] / dist;  // MapPoint::PredictScale src/MapPoint.cc:378 (the raw mfMaxDistance)
-      int nScale = (int)ceilf(uvo_logf(ratio) / log_sf);
+      // a quotient that does not fit an int (+inf when ratio overflows, NaN) converts to INT_MIN in the reference's x86-64 build
+      const float q = ceilf(uvo_logf(ratio) / log_sf);
+      int nScale = q < 2147483648.f ? (int)q : (-2147483647 - 1);
       if (nScale < 0)
         nScale = 0;
       else if (nScale >= nlevels)
