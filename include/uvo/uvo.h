@@ -751,7 +751,9 @@ typedef struct uvo_vocabulary uvo_vocabulary;
 typedef struct uvo_vocabulary_desc {
   int32_t n_nodes;            /* m_nodes.size(); node 0 is the root */
   const int32_t* child_start; /* [n_nodes + 1]: children of node i = children[child_start[i] .. child_start[i+1]), in m_nodes[i].children order */
-  const int32_t* children;
+  const int32_t* children;    /* ids in 1..n_nodes-1, each at most once: a tree, as every DBoW2 vocabulary is.  A description that lists a
+                                 node twice (its own descendant, or under two parents) is refused with UVO_E_BADARG: the root is never a
+                                 child, so a descent from it cannot re-enter a node and always ends */
   const uint8_t* descriptor;  /* [n_nodes][32]: m_nodes[i].descriptor (row 0 unused) */
   const int32_t* word_id;     /* [n_nodes]: m_nodes[i].word_id (read for leaves) */
   const double* weight;       /* [n_nodes]: m_nodes[i].weight */

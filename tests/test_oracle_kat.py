@@ -1,12 +1,14 @@
 """Known-answer tests that pin the CPU oracle (the reference has no tests or fixtures of its own,
 so every answer here is hand-derivable from the reference sources, or cross-checked by an independent numpy
-formulation written in this file)."""
+formulation written in this file, or for CLAHE in tests/side_model.py)."""
 import ctypes
 import subprocess
 import os
 
 import numpy as np
 import pytest
+
+from side_model import clahe as _clahe_numpy   # the numpy statement of OpenCV 3.4's 8-bit CLAHE, kept with the other models
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -469,46 +471,6 @@ def test_grider_fast(oracle, synth):
 
 
 # ---- CLAHE (cv::CLAHE::apply, src/Tracking.cc:425-431) ------------------------------------------------------------------
-def _clahe_numpy(img, clip_limit, tiles):
-    """Independent numpy statement of OpenCV 3.4's 8-bit CLAHE (vectorised differently from the oracle's loops)."""
-    tx, ty = tiles
-    h, w = img.shape
-    if w % tx == 0 and h % ty == 0:
-        ext = img
-    else:
-        ext = np.pad(img, ((0, ty - h % ty), (0, tx - w % tx)), mode="reflect")
-    tw, th = ext.shape[1] // tx, ext.shape[0] // ty
-    total = tw * th
-    scale = np.float32(255) / np.float32(total)
-    clip = max(int(clip_limit * total / 256), 1) if clip_limit > 0 else 0
-    luts = np.zeros((ty, tx, 256), np.float32)
-    for j in range(ty):
-        for i in range(tx):
-            hist = np.bincount(ext[j * th:(j + 1) * th, i * tw:(i + 1) * tw].ravel(), minlength=256).astype(np.int64)
-            if clip > 0:
-                clipped = int(np.maximum(hist - clip, 0).sum())
-                hist = np.minimum(hist, clip) + clipped // 256
-                residual = clipped % 256
-                if residual:
-                    step = max(256 // residual, 1)
-                    idx = np.arange(0, 256, step)[:residual]
-                    hist[idx] += 1
-            luts[j, i] = np.clip(np.rint(np.cumsum(hist).astype(np.float32) * scale), 0, 255)
-    xs, ys = np.arange(w, dtype=np.float32), np.arange(h, dtype=np.float32)
-    txf = xs * (np.float32(1) / np.float32(tw)) - np.float32(0.5)
-    tyf = ys * (np.float32(1) / np.float32(th)) - np.float32(0.5)
-    tx1, ty1 = np.floor(txf).astype(int), np.floor(tyf).astype(int)
-    xa, ya = (txf - tx1.astype(np.float32)).astype(np.float32), (tyf - ty1.astype(np.float32)).astype(np.float32)
-    xa1, ya1 = np.float32(1) - xa, np.float32(1) - ya
-    tx2, ty2 = np.minimum(tx1 + 1, tx - 1), np.minimum(ty1 + 1, ty - 1)
-    tx1, ty1 = np.maximum(tx1, 0), np.maximum(ty1, 0)
-    v = img.astype(int)
-    p11, p12 = luts[ty1[:, None], tx1[None, :], v], luts[ty1[:, None], tx2[None, :], v]
-    p21, p22 = luts[ty2[:, None], tx1[None, :], v], luts[ty2[:, None], tx2[None, :], v]
-    res = (p11 * xa1[None, :] + p12 * xa[None, :]) * ya1[:, None] + (p21 * xa1[None, :] + p22 * xa[None, :]) * ya[:, None]
-    return np.clip(np.rint(res.astype(np.float32)), 0, 255).astype(np.uint8)
-
-
 def test_clahe_by_hand_and_against_numpy(oracle, synth):
     flat = np.full((8, 8), 10, np.uint8)
     # 2 x 2 tiles of 16 px, no clipping: lut = 0 below 10, 255 from 10 on

@@ -59,6 +59,12 @@ int uvo_vocabulary_create(const uvo_vocabulary_desc* d, uvo_vocabulary** out) {
   if (nch > 0 && !d->children) return fail(UVO_E_BADARG, "null children");
   for (int c = 0; c < nch; ++c)
     if (d->children[c] <= 0 || d->children[c] >= d->n_nodes) return fail(UVO_E_BADARG, "child id outside 1..n_nodes-1");
+  // every node is a child at most once: with the root never a child, no descent from the root re-enters a node, so each one ends
+  std::vector<bool> listed((size_t)d->n_nodes, false);
+  for (int c = 0; c < nch; ++c) {
+    if (listed[(size_t)d->children[c]]) return fail(UVO_E_BADARG, "a node is listed as a child more than once (not a tree)");
+    listed[(size_t)d->children[c]] = true;
+  }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(UVO_E_NODEVICE, "no HIP device available (no CPU fallback exists)");
   if (d->device < 0 || d->device >= ndev) return fail(UVO_E_BADARG, "device ordinal out of range");
