@@ -1143,6 +1143,81 @@ int uvo_initializer_initialize(uvo_initializer* init, const float* keys2_xy, int
  * *n = hypotheses written (0 after a call with n2 < 8). */
 int uvo_initializer_hypotheses(uvo_initializer* init, int32_t* subsets, float* F, float* scores, int cap, int* n);
 
+/* ------------------------------------------------------------------------------------------------------------------------------
+ * Keyframe database -- replaces USLAM::KeyFrameDatabase (include/KeyFrameDatabase.h, src/KeyFrameDatabase.cc) as the first step of
+ * Tracking::Relocalisation (src/Tracking.cc:2373-2379: DetectRelocalisationCandidates) and of LoopClosing::DetectLoop
+ * (src/LoopClosing.cc:195-196: DetectLoopCandidates, DetectLoopCandidatesHaloc).  The keyframes' BoW vectors, haloc hashes, covisible
+ * rows and the six per-keyframe query fields of the reference live on the device; ONE call answers a query: per-keyframe common-word
+ * count, first common word, L1 score and hash distance in parallel, then the ordered epilogue, with no host round trip between.
+ * Only the L1 score is built (DBoW2::L1Scoring, Thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-68): it is what ORBvoc declares; the other
+ * scorings, DetectLoop's own prologue (src/LoopClosing.cc:155-188) and the cluster candidates (getCandidates_haloc,
+ * getCandidates_Proximity) do not exist here.
+ * A keyframe keeps the slot uvo_kfdb_add gave it until uvo_kfdb_clear.  The six fields persist between queries as the reference's do:
+ * a query reads the values an earlier one left (a neighbour's score from an earlier query with the same id is added again).
+ * Departures from the reference: (1) the mRelocScore / mLoopScore of a keyframe never scored since its add is 0.0f (the reference
+ * reads an uninitialised float); (2) uvo_kfdb_clear drops the hash list too (the reference keeps dangling pointers in kfVec);
+ * (3) the haloc matches are ordered by (distance, add order): the reference's std::sort leaves the order of equal distances open;
+ * (4) a covisible neighbour that has no slot (-1) is skipped.  Semantics pinned to the sources by tests/kfdb_model.py; every float
+ * is bit-exact.
+ */
+#define UVO_KFDB_COVISIBLES 10 /* GetBestCovisibilityKeyFrames(10) */
+#define UVO_KFDB_LISTED 1      /* uvo_kfdb_query_row.flags: in lKFsSharingWords (always set) */
+#define UVO_KFDB_SCORED 2      /* words > minCommonWords: the score was computed and stored */
+#define UVO_KFDB_ENTERED 4     /* in lScoreAndMatch (loop: si >= minScore): acc and best are valid */
+#define UVO_KFDB_RETAINED 8    /* acc > 0.75f * bestAccScore (before the first-occurrence dedup of best) */
+typedef struct uvo_kfdb uvo_kfdb;
+typedef struct uvo_kfdb_fields { /* the reference's per-keyframe query fields */
+  int64_t loop_query;   /* mnLoopQuery, 0 at add */
+  int64_t reloc_query;  /* mnRelocQuery, 0 at add */
+  int32_t loop_words;   /* mnLoopWords, 0 at add */
+  int32_t reloc_words;  /* mnRelocWords, 0 at add */
+  float loop_score;     /* mLoopScore, 0.0f at add */
+  float reloc_score;    /* mRelocScore, 0.0f at add */
+} uvo_kfdb_fields;
+typedef struct uvo_kfdb_query_row { /* one keyframe of lKFsSharingWords, in list order */
+  int32_t slot;
+  int32_t words; /* mn{Loop,Reloc}Words after the walk */
+  int32_t flags; /* UVO_KFDB_* */
+  int32_t best;  /* pBestKF's slot, -1 unless ENTERED */
+  float score;   /* the stored m{Loop,Reloc}Score after the scoring loop (a stale value unless SCORED) */
+  float acc;     /* accScore, 0 unless ENTERED */
+} uvo_kfdb_query_row;
+/* max_keyframes 1..65536 slots, max_words 1..4096 (longest BoW vector, of a keyframe or a query), hash_len 1..4096 floats. */
+int uvo_kfdb_create(int max_keyframes, int max_words, int hash_len, int device, uvo_kfdb** out);
+void uvo_kfdb_destroy(uvo_kfdb* db);
+/* KeyFrameDatabase::add (:39-46): id = mnId; the BoW vector as uvo_bow_transform emits it (n_bow ids strictly ascending, else
+ * UVO_E_BADARG; n_bow 0 allowed); hash = GetHalocVector(), hash_len floats, NULL for an empty one.  One row upload, no reallocation:
+ * UVO_E_CAPACITY when every slot is taken or n_bow > max_words. */
+int uvo_kfdb_add(uvo_kfdb* db, int64_t id, const uint32_t* bow_id, const double* bow_value, int n_bow, const float* hash, int* slot);
+/* KeyFrameDatabase::erase (:48-67): out of the BoW queries only; the haloc query still sees the keyframe (kfVec is never pruned) and its
+ * state stays readable as a neighbour's.  Erasing twice is a no-op; a slot that holds no keyframe: UVO_E_BADARG. */
+int uvo_kfdb_erase(uvo_kfdb* db, int slot);
+/* KeyFrameDatabase::clear (:69-73), and every slot freed. */
+int uvo_kfdb_clear(uvo_kfdb* db);
+/* GetBestCovisibilityKeyFrames(10) of the keyframe in slot, in its order: n <= 10 slots, -1 for a neighbour without one; empty at add.
+ * n > 10 or a neighbour that is neither -1 nor a held slot: UVO_E_BADARG. */
+int uvo_kfdb_set_covisibles(uvo_kfdb* db, int slot, const int32_t* neigh_slots, int n);
+/* DetectRelocalisationCandidates(F): query_id = F->mnId, the frame's BoW vector (n_bow <= max_words, ascending).  cand_slot[0..*n_cand)
+ * = vpRelocCandidates in order; *n_cand > cap: UVO_E_CAPACITY, nothing written to cand_slot (the state has been updated). */
+int uvo_kfdb_detect_reloc(uvo_kfdb* db, int64_t query_id, const uint32_t* bow_id, const double* bow_value, int n_bow, int32_t* cand_slot, int cap,
+                          int* n_cand);
+/* DetectLoopCandidates(pKF, minScore): connected_slots = the slots of pKF->GetConnectedKeyFrames() (those that have one). */
+int uvo_kfdb_detect_loop(uvo_kfdb* db, int64_t query_id, const uint32_t* bow_id, const double* bow_value, int n_bow, const int32_t* connected_slots,
+                         int n_connected, float min_score, int32_t* cand_slot, int cap, int* n_cand);
+/* DetectLoopCandidatesHaloc(pKF, maxScore, haloc): hash = pKF->GetHalocVector() (NULL: empty); exclude_ids = no_candidates (mnIds,
+ * n_exclude <= max_keyframes).  *n_cand is 3 or 0: the reference returns its best three only when at least three matches were kept
+ * (:125-132) and nothing otherwise. */
+int uvo_kfdb_detect_loop_haloc(uvo_kfdb* db, int64_t query_id, const float* hash, const int64_t* exclude_ids, int n_exclude, float max_score,
+                               int32_t cand_slot[3], int* n_cand);
+/* test taps.  _last_query: lKFsSharingWords of the last BoW query in list order (*n rows; UVO_E_CAPACITY when cap is smaller), with
+ * maxCommonWords and minCommonWords.  _last_haloc: per slot the distance m of the last haloc query and whether it was kept (a slot
+ * skipped as the query itself or as excluded: m = 0, kept = 0).  _state: the fields of n slots from first_slot on. */
+int uvo_kfdb_last_query(uvo_kfdb* db, uvo_kfdb_query_row* rows, int cap, int* n, int* max_common, int* min_common);
+int uvo_kfdb_last_haloc(uvo_kfdb* db, float* m, uint8_t* kept, int cap, int* n);
+int uvo_kfdb_state(uvo_kfdb* db, int first_slot, int n, uvo_kfdb_fields* out);
+/* slots handed out since the last clear */
+int uvo_kfdb_size(uvo_kfdb* db);
+
 /* last HIP / argument error text for the calling thread's most recent failing call (never NULL) */
 const char* uvo_last_error(void);
 /* library + device description, e.g. "uvo 0.1 gfx950 AMD Instinct MI355X" */

@@ -48,6 +48,8 @@ ABI_SYMBOLS = [
     "uvo_sim3solver_set_create", "uvo_sim3solver_set_destroy", "uvo_sim3solver_set_clear", "uvo_sim3solver_add", "uvo_sim3solver_set_ransac_parameters",
     "uvo_sim3solver_query", "uvo_sim3solver_iterate", "uvo_sim3solver_find", "uvo_sim3solver_hypotheses",
     "uvo_initializer_create", "uvo_initializer_destroy", "uvo_initializer_set_reference", "uvo_initializer_initialize", "uvo_initializer_hypotheses",
+    "uvo_kfdb_create", "uvo_kfdb_destroy", "uvo_kfdb_add", "uvo_kfdb_erase", "uvo_kfdb_clear", "uvo_kfdb_set_covisibles", "uvo_kfdb_detect_reloc",
+    "uvo_kfdb_detect_loop", "uvo_kfdb_detect_loop_haloc", "uvo_kfdb_last_query", "uvo_kfdb_last_haloc", "uvo_kfdb_state", "uvo_kfdb_size",
     "uvo_matcher_kernel_times", "uvo_last_error", "uvo_device_info",
 ]
 
@@ -293,6 +295,21 @@ def _load():
     lib.uvo_initializer_set_reference.argtypes = [vp, vp, ci, vp, cf, ci]
     lib.uvo_initializer_initialize.argtypes = [vp, vp, ci, vp, vp, vp]
     lib.uvo_initializer_hypotheses.argtypes = [vp, vp, vp, vp, ci, vp]
+    i64 = ctypes.c_int64
+    lib.uvo_kfdb_create.argtypes = [ci, ci, ci, ci, vp]
+    lib.uvo_kfdb_destroy.argtypes = [vp]
+    lib.uvo_kfdb_destroy.restype = None
+    lib.uvo_kfdb_add.argtypes = [vp, i64, vp, vp, ci, vp, vp]
+    lib.uvo_kfdb_erase.argtypes = [vp, ci]
+    lib.uvo_kfdb_clear.argtypes = [vp]
+    lib.uvo_kfdb_set_covisibles.argtypes = [vp, ci, vp, ci]
+    lib.uvo_kfdb_detect_reloc.argtypes = [vp, i64, vp, vp, ci, vp, ci, vp]
+    lib.uvo_kfdb_detect_loop.argtypes = [vp, i64, vp, vp, ci, vp, ci, cf, vp, ci, vp]
+    lib.uvo_kfdb_detect_loop_haloc.argtypes = [vp, i64, vp, vp, ci, cf, vp, vp]
+    lib.uvo_kfdb_last_query.argtypes = [vp, vp, ci, vp, vp, vp]
+    lib.uvo_kfdb_last_haloc.argtypes = [vp, vp, vp, ci, vp]
+    lib.uvo_kfdb_state.argtypes = [vp, ci, ci, vp]
+    lib.uvo_kfdb_size.argtypes = [vp]
     lib.uvo_fuse.argtypes = [vp, vp, ci, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, ci, cf, vp, vp]
     lib.uvo_search_for_triangulation_batch.argtypes = [vp, vp, vp, ci, vp, vp, ci, vp]
     lib.uvo_search_for_triangulation_next.argtypes = [vp, ci, vp, ci, vp, vp]
@@ -1649,6 +1666,136 @@ class Initializer:
         if rc:
             raise UvoError(rc, "uvo_initializer_hypotheses")
         return sub[:n.value].copy(), F[:n.value].copy(), sc[:n.value].copy()
+
+
+KFDB_STATE_DTYPE = np.dtype([("loop_query", np.int64), ("reloc_query", np.int64), ("loop_words", np.int32), ("reloc_words", np.int32),
+                             ("loop_score", np.float32), ("reloc_score", np.float32)])                      # uvo_kfdb_state
+KFDB_ROW_DTYPE = np.dtype([("slot", np.int32), ("words", np.int32), ("flags", np.int32), ("best", np.int32), ("score", np.float32),
+                           ("acc", np.float32)])                                                             # uvo_kfdb_query_row
+KFDB_LISTED, KFDB_SCORED, KFDB_ENTERED, KFDB_RETAINED = 1, 2, 4, 8
+
+
+class KeyFrameDatabase:
+    """USLAM::KeyFrameDatabase (src/KeyFrameDatabase.cc) held on the device: add / erase / clear and the three Detect* queries, one call
+    each.  Keyframes are named by the slot add() returns; BoW vectors are (ids uint32 ascending, values float64) as ORBVocabulary.transform
+    returns them.  `_api` / `_prefix` exist so that the tests' host build of the same rules can be driven through this very class."""
+    _prefix = "uvo_kfdb_"
+
+    def __init__(self, max_keyframes, max_words, hash_len, device=0, _api=None):
+        self._api = _api if _api is not None else lib
+        self.max_keyframes, self.max_words, self.hash_len = int(max_keyframes), int(max_words), int(hash_len)
+        self._h = ctypes.c_void_p()
+        rc = self._f("create")(self.max_keyframes, self.max_words, self.hash_len, int(device), ctypes.byref(self._h))
+        if rc:
+            raise UvoError(rc, "uvo_kfdb_create")
+
+    def _f(self, name):
+        return getattr(self._api, self._prefix + name)
+
+    def close(self):
+        if getattr(self, "_h", None) and self._api is not None:
+            self._f("destroy")(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __len__(self):
+        return self._f("size")(self._h)
+
+    @staticmethod
+    def _bow(bow):
+        ids, vals = np.ascontiguousarray(bow[0], np.uint32).reshape(-1), np.ascontiguousarray(bow[1], np.float64).reshape(-1)
+        if len(ids) != len(vals):
+            raise ValueError("BoW ids and values differ in length")
+        return ids, vals
+
+    def _hash(self, h):
+        if h is None:
+            return None
+        h = np.ascontiguousarray(h, np.float32).reshape(-1)
+        if len(h) != self.hash_len:
+            raise ValueError("hash of %d floats, the database holds %d" % (len(h), self.hash_len))
+        return h
+
+    def add(self, mn_id, bow, hash=None):
+        """KeyFrameDatabase::add: returns the keyframe's slot."""
+        ids, vals = self._bow(bow)
+        h, slot = self._hash(hash), ctypes.c_int()
+        rc = self._f("add")(self._h, int(mn_id), _ptr(ids), _ptr(vals), len(ids), _ptr(h), ctypes.byref(slot))
+        if rc:
+            raise UvoError(rc, "uvo_kfdb_add")
+        return slot.value
+
+    def erase(self, slot):
+        rc = self._f("erase")(self._h, int(slot))
+        if rc:
+            raise UvoError(rc, "uvo_kfdb_erase")
+
+    def clear(self):
+        rc = self._f("clear")(self._h)
+        if rc:
+            raise UvoError(rc, "uvo_kfdb_clear")
+
+    def set_covisibles(self, slot, neigh_slots):
+        """GetBestCovisibilityKeyFrames(10) of the keyframe in `slot`, as slots in its order (-1: a neighbour without one)."""
+        nb = np.ascontiguousarray(neigh_slots, np.int32).reshape(-1)
+        rc = self._f("set_covisibles")(self._h, int(slot), _ptr(nb), len(nb))
+        if rc:
+            raise UvoError(rc, "uvo_kfdb_set_covisibles")
+
+    def detect_reloc(self, query_id, bow):
+        """DetectRelocalisationCandidates: the candidates' slots, in the reference's order."""
+        ids, vals = self._bow(bow)
+        cand, n = np.zeros(max(self.max_keyframes, 1), np.int32), ctypes.c_int()
+        rc = self._f("detect_reloc")(self._h, int(query_id), _ptr(ids), _ptr(vals), len(ids), _ptr(cand), len(cand), ctypes.byref(n))
+        if rc:
+            raise UvoError(rc, "uvo_kfdb_detect_reloc")
+        return cand[:n.value].copy()
+
+    def detect_loop(self, query_id, bow, connected_slots, min_score):
+        """DetectLoopCandidates(pKF, minScore); connected_slots: the slots of pKF->GetConnectedKeyFrames()."""
+        ids, vals = self._bow(bow)
+        conn = np.ascontiguousarray(connected_slots, np.int32).reshape(-1)
+        cand, n = np.zeros(max(self.max_keyframes, 1), np.int32), ctypes.c_int()
+        rc = self._f("detect_loop")(self._h, int(query_id), _ptr(ids), _ptr(vals), len(ids), _ptr(conn), len(conn), float(min_score), _ptr(cand), len(cand),
+                                    ctypes.byref(n))
+        if rc:
+            raise UvoError(rc, "uvo_kfdb_detect_loop")
+        return cand[:n.value].copy()
+
+    def detect_loop_haloc(self, query_id, hash, exclude_ids, max_score):
+        """DetectLoopCandidatesHaloc: three slots, or none when fewer than three matches were kept."""
+        h, ex = self._hash(hash), np.ascontiguousarray(exclude_ids, np.int64).reshape(-1)
+        cand, n = np.zeros(3, np.int32), ctypes.c_int()
+        rc = self._f("detect_loop_haloc")(self._h, int(query_id), _ptr(h), _ptr(ex), len(ex), float(max_score), _ptr(cand), ctypes.byref(n))
+        if rc:
+            raise UvoError(rc, "uvo_kfdb_detect_loop_haloc")
+        return cand[:n.value].copy()
+
+    def last_query(self):
+        """Test tap: (rows KFDB_ROW_DTYPE[n] in list order, maxCommonWords, minCommonWords) of the last BoW query."""
+        rows, n, mx, mn = np.zeros(max(self.max_keyframes, 1), KFDB_ROW_DTYPE), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        rc = self._f("last_query")(self._h, _ptr(rows), len(rows), ctypes.byref(n), ctypes.byref(mx), ctypes.byref(mn))
+        if rc:
+            raise UvoError(rc, "uvo_kfdb_last_query")
+        return rows[:n.value].copy(), mx.value, mn.value
+
+    def last_haloc(self):
+        """Test tap: (m float32[slots], kept uint8[slots]) of the last haloc query."""
+        m, kept, n = np.zeros(max(self.max_keyframes, 1), np.float32), np.zeros(max(self.max_keyframes, 1), np.uint8), ctypes.c_int()
+        rc = self._f("last_haloc")(self._h, _ptr(m), _ptr(kept), len(m), ctypes.byref(n))
+        if rc:
+            raise UvoError(rc, "uvo_kfdb_last_haloc")
+        return m[:n.value].copy(), kept[:n.value].copy()
+
+    def state(self):
+        """The six persistent fields of every slot, KFDB_STATE_DTYPE[len(self)]."""
+        n = len(self)
+        out = np.zeros(max(n, 1), KFDB_STATE_DTYPE)
+        rc = self._f("state")(self._h, 0, n, _ptr(out))
+        if rc:
+            raise UvoError(rc, "uvo_kfdb_state")
+        return out[:n].copy()
 
 
 class KltCfg(ctypes.Structure):
