@@ -110,6 +110,27 @@ def test_consecutive_calls_on_one_generator_and_a_new_reference(uvo, pair):
     assert gd.state() == ref.state()
 
 
+def test_an_object_filled_to_capacity_equals_one_with_room_to_spare(uvo, emu, klt):
+    """max_keys = n1 = n2 = 65: the last element of every array of the object's block and of both exchanges is written and read, the mask
+    spans two 64-bit words; the call equals, bit for bit, the one on an object of 256 keys and the host build's."""
+    k1, k2, m12, _ = ic.scene(65, 65, 0.1)
+    place = np.random.RandomState(65).permutation(65)         # the 65 matched reference keys alone, shuffled: every reference key is named
+    ref = np.zeros((65, 2), np.float32)
+    ref[place] = k1[m12]
+    sc = (ref, k2, place.astype(np.int32))
+    calls = []
+    for make in (lambda: uvo.Initializer(klt, 65), lambda: uvo.Initializer(klt, 256), lambda: emu.make(uvo, 65)):
+        obj = make()
+        try:
+            calls.append(ic.run(obj, uvo, sc, rng=uvo.GlibcRand(1)))
+        finally:
+            obj.close()
+    ic.assert_calls_equal(calls[0], calls[1], "65 keys against 256")
+    ic.assert_calls_equal(calls[0], calls[2], "65 keys against the host build")
+    r = calls[0].result
+    assert r.initialized and r.inliers[64] == 1 and r.triangulated[64] == 1 and r.p3d[64].any() and len(calls[0].sets) == 200
+
+
 def test_out_of_range_match_and_capacity(uvo, pair):
     dev = pair[0]
     k1, k2, m12, _ = ic.scene(0, 16, 0.0)

@@ -28,6 +28,24 @@ def test_two_databases_do_not_share_state(uvo):
     assert got_a == want and got_b[1:] == want
 
 
+def test_a_database_filled_to_capacity_equals_one_with_room_to_spare(uvo):
+    """KeyFrameDatabase(3, 4, 2) holding three keyframes of four words and two hash floats each: the last element of every per-slot array and
+    of every mirror is written and read; the answers are the model's, and those of a database of (24, 32, 2)."""
+    W = kc.W
+    ops = [("add", 7, *kc.bow(W[0:4], [0.25] * 4), kc._h(1, 0)), ("add", 5, *kc.bow(W[1:5], [0.4, 0.3, 0.2, 0.1]), kc._h(0, 2)),
+           ("add", 6, *kc.bow([W[0], W[2], W[3], W[6]], [0.125, 0.5, 0.25, 0.125]), kc._h(0.5, 0.5)),
+           ("cov", 0, [2, 1]), ("cov", 1, [0]), ("cov", 2, [1, 0]),
+           ("reloc", 1, *kc.bow(W[0:4], [0.25] * 4)), ("loop", 2, *kc.bow(W[1:5], [0.25] * 4), [0], kc.F32(0.05)),
+           ("haloc", 99, kc._h(0, 0), [], kc.F32(4.0)), ("reloc", 3, *kc.bow(W[2:4], [0.5, 0.5]))]
+    want = kc.run_model((3, 4, 2, ops))
+    tight = kc.run_api((3, 4, 2, ops), lambda k, w, h: uvo.KeyFrameDatabase(k, w, h))
+    roomy = kc.run_api((24, 32, 2, ops), lambda k, w, h: uvo.KeyFrameDatabase(k, w, h))
+    assert tight == want, kc.explain(tight, want, (3, 4, 2, ops))
+    assert roomy == want
+    queries = [w for w in want if isinstance(w, dict)]
+    assert 2 in [r[0] for r in queries[0]["rows"]] and queries[3]["cand"] == [2]             # the last slot is listed, and is a candidate
+
+
 def _refused(uvo, code, fn, *args):
     with pytest.raises(uvo.UvoError) as ei:
         fn(*args)

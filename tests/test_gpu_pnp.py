@@ -120,6 +120,22 @@ def test_a_thousand_iterations_reach_the_cap(klt, uvo, emu):
     assert g.iterations > 300
 
 
+def test_a_handle_sized_for_exactly_the_call(klt, uvo, emu):
+    """KLT(max_points = n) for a call of n points: the last element of every per-point array of the scratch block and of its page-locked
+    mirror is written and read (the last point is an inlier); the run equals the host
+    build's and the one on the module's larger handle bit for bit."""
+    cam, obj, img, _, _, _ = pm.scene(7, 70, 1.0, 0.3)
+    tight = uvo.KLT(64, 64, max_points=70)
+    try:
+        g = pc.gpu_run(tight, uvo, cam, obj, img)
+    finally:
+        tight.close()
+    pc.check_layers_1_to_3(g, cam, obj, img, what="max_points = n")
+    assert_bitwise_equal_runs(g, emu.run(cam, obj, img), "max_points = n")
+    assert_bitwise_equal_runs(g, pc.gpu_run(klt, uvo, cam, obj, img), "max_points = n against the larger handle")
+    assert g.ok == 1 and g.inliers[-1] == 69
+
+
 def test_fewer_than_five_points_touch_nothing(klt, uvo):
     cam, obj, img, _, _, _ = pm.scene(3, 8, 1.0, 0.3)
     for n in range(5):

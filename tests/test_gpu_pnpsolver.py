@@ -138,6 +138,19 @@ def test_capacity_edges(uvo, emu, klt):
         pset.close()
 
 
+def test_a_set_filled_to_capacity_equals_one_with_room_to_spare(uvo, emu, klt):
+    """Both solvers of a (2, 65) set hold 65 points -- the last element of every array of the set's block is written and read, the inlier
+    set spans two 64-bit words -- and the session equals, bit for bit, the one on an (8, 256) set, where every array lies elsewhere."""
+    cands = [psm.candidate(301, 65, 0.2), psm.candidate(302, 65, 0.8, 0.5, n_matches=65)]
+    calls = [([0, 1], 5), ([1, 0], 5)]
+    tight = both(uvo, emu, klt, cands, calls, what="(2, 65)")
+    roomy = both(uvo, emu, klt, cands, calls, max_solvers=8, max_points=256, what="(8, 256)")
+    pc.assert_sessions_equal(tight, roomy, "(2, 65) against (8, 256)")
+    r = tight[0].result
+    assert (r.returned, r.solver) == (1, 1) and r.status[0].tolist() == [1, 1, 35] and len(r.inliers) == 65
+    assert r.inliers[cands[1][3][64]] == 1                                                          # bit 0 of the second word
+
+
 def test_find_is_iterate_of_max_its(uvo, emu, klt):
     cands = [psm.candidate(90, 40, 0.75)]
     dev, host = uvo.PnPsolverSet(klt, 1, 40), emu.make_set(uvo, 1, 40)

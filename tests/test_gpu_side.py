@@ -288,10 +288,11 @@ def test_bow_capacity_exact_and_one_less(uvo):
 
 
 def test_bow_handle_grows_then_takes_a_small_call(uvo):
-    """130, then 5000, then 3 features through one handle: the staging grows, then holds stale rows past the third."""
+    """130, then 5000, then 3, then 130 features through one handle: the staging grows (its four buffers are released and allocated anew),
+    then holds stale rows past the third and the fourth."""
     voc = sc.build_vocabulary([10, 10, 10], 3)
     V = _vocabulary(uvo, voc)
-    for n in (130, 5000, 3):
+    for n in (130, 5000, 3, 130):
         feats = sc.bow_features(voc, n, 9000 + n)
         assert same_bow(_as_oracle_form(V.transform(feats, 1)), sm.bow_transform(voc, feats, 1)), n
     V.close()

@@ -134,6 +134,18 @@ def test_max_solvers_and_max_points_once(uvo, emu, matcher):
     assert r.solver == 63 and r.n_inliers > 5000 and len(r.inliers) == 16400 and r.status[:, 0].all()
 
 
+def test_a_set_filled_to_capacity_equals_one_with_room_to_spare(uvo, emu, matcher):
+    """Both solvers of a (2, 65) set hold 65 points -- the last element of every array of the set's block is written and read, the inlier
+    set spans two 64-bit words -- and the session equals, bit for bit, the one on an (8, 256) set, where every array lies elsewhere."""
+    cands = [sm.candidate(2065, 65, 0.3, 0.5, n_matches=74), sm.candidate(2166, 65, 0.9, 0.5)]
+    calls = [([0, 1], 5), ([1, 0], 5), ([0], 1)]
+    tight = both(uvo, emu, matcher, cands, calls, what="(2, 65)")
+    roomy = both(uvo, emu, matcher, cands, calls, max_solvers=8, max_points=256, what="(8, 256)")
+    sc.assert_sessions_equal(tight, roomy, "(2, 65) against (8, 256)")
+    r = tight[0].result
+    assert (r.returned, r.solver) == (1, 1) and r.inliers[cands[1][4][64]] == 1                    # bit 0 of the second word
+
+
 def test_degenerate_inputs_leave_no_nan(uvo, emu, matcher):
     x1w, x2w, sg1, sg2, index1, nm, kf1, kf2, _ = sm.candidate(5, 40, 0.9)
     same = (np.tile(x1w[:1], (40, 1)), np.tile(x2w[:1], (40, 1)), sg1, sg2, index1, nm, kf1, kf2)

@@ -5,13 +5,14 @@
 #include <map>
 #include <vector>
 
-#include "common.hpp"
+#include "devmem.hpp"
 
 using namespace uvo;
 
 struct uvo_vocabulary {
   int device = 0, n_nodes = 0, L = 0, weighting = 0, normalize = 0;
   hipStream_t stream = nullptr;
+  DevMem mem;  // owns every d_*
   int32_t *d_child_start = nullptr, *d_children = nullptr, *d_word_id = nullptr;
   uint8_t* d_desc = nullptr;
   double* d_weight = nullptr;
@@ -22,25 +23,13 @@ struct uvo_vocabulary {
   int cap = 0;
 };
 
-template <class T>
-static int v_alloc(T** p, size_t n) {
-  hipError_t e = hipMalloc((void**)p, (n ? n : 1) * sizeof(T));
-  if (e != hipSuccess) {
-    hip_err_set(e, "hipMalloc");
-    return e == hipErrorOutOfMemory ? UVO_E_NOMEM : UVO_E_HIP;
-  }
-  return UVO_OK;
-}
-
 extern "C" {
 
 void uvo_vocabulary_destroy(uvo_vocabulary* v) {
   if (!v) return;
   hipSetDevice(v->device);
   if (v->stream) hipStreamSynchronize(v->stream);
-  void* ptrs[] = {v->d_child_start, v->d_children, v->d_word_id, v->d_desc, v->d_weight, v->d_feat, v->d_word, v->d_node, v->d_w};
-  for (void* p : ptrs)
-    if (p) hipFree(p);
+  v->mem.release_all();
   if (v->stream) hipStreamDestroy(v->stream);
   delete v;
 }
@@ -75,9 +64,10 @@ int uvo_vocabulary_create(const uvo_vocabulary_desc* d, uvo_vocabulary** out) {
     return fail(UVO_E_HIP, "stream creation failed");
   }
   const size_t N = (size_t)d->n_nodes;
+  DevMem& m = v->mem;
   int rc;
-  if ((rc = v_alloc(&v->d_child_start, N + 1)) || (rc = v_alloc(&v->d_children, (size_t)nch)) || (rc = v_alloc(&v->d_word_id, N)) ||
-      (rc = v_alloc(&v->d_desc, N * 32)) || (rc = v_alloc(&v->d_weight, N))) {
+  if ((rc = m.alloc(&v->d_child_start, N + 1)) || (rc = m.alloc(&v->d_children, (size_t)nch)) || (rc = m.alloc(&v->d_word_id, N)) ||
+      (rc = m.alloc(&v->d_desc, N * 32)) || (rc = m.alloc(&v->d_weight, N))) {
     uvo_vocabulary_destroy(v);
     return rc;
   }
@@ -106,12 +96,12 @@ int uvo_bow_transform(uvo_vocabulary* v, const uint8_t* desc, int n, int levelsu
   hipStream_t s = v->stream;
   if (n > v->cap) {
     UVO_HIP_CHECK(hipStreamSynchronize(s));
-    for (void* p : {(void*)v->d_feat, (void*)v->d_word, (void*)v->d_node, (void*)v->d_w})
-      if (p) hipFree(p);
-    v->d_feat = nullptr, v->d_word = nullptr, v->d_node = nullptr, v->d_w = nullptr;
+    DevMem& m = v->mem;
+    for (void* p : {(void*)v->d_feat, (void*)v->d_word, (void*)v->d_node, (void*)v->d_w}) m.release(p);
+    v->d_feat = nullptr, v->d_word = nullptr, v->d_node = nullptr, v->d_w = nullptr, v->cap = 0;  // until all four are there again
     const size_t c = (size_t)n * 2 + 256;
     int rc;
-    if ((rc = v_alloc(&v->d_feat, c * 32)) || (rc = v_alloc(&v->d_word, c)) || (rc = v_alloc(&v->d_node, c)) || (rc = v_alloc(&v->d_w, c))) return rc;
+    if ((rc = m.alloc(&v->d_feat, c * 32)) || (rc = m.alloc(&v->d_word, c)) || (rc = m.alloc(&v->d_node, c)) || (rc = m.alloc(&v->d_w, c))) return rc;
     v->cap = (int)c;
   }
   UVO_HIP_CHECK(hipMemcpyAsync(v->d_feat, desc, (size_t)n * 32, hipMemcpyHostToDevice, s));

@@ -10,7 +10,7 @@
 #include <mutex>
 #include <vector>
 
-#include "common.hpp"
+#include "devmem.hpp"
 #include "profiler.hpp"
 #include "tune_internal.h"
 
@@ -25,25 +25,6 @@ constexpr int kMaxLanes = 4;
 constexpr int kTilePyramidFrames = 8;  // batches up to this size build the pyramid in one k_pyr_tiles launch
 constexpr int kFewFrames = 2;  // batches up to this size are the latency path (the FAST kernels cut their segments short for them: fast_rows_per_seg)
 constexpr int kSmallBatch = 16;  // host-buffer calls: above this the caller-side copies are a small part of the call
-
-// Device and page-locked memory of one owner (a lane, or the handle): a buffer is freed because it was allocated here, not because a
-// list names it.  No pool and no reuse -- a registry.
-struct DevMem {
-  struct Block {
-    void* p;
-    size_t bytes;
-    bool pinned;
-  };
-  std::vector<Block> blocks;
-  int alloc_bytes(void** p, size_t bytes, bool pinned);  // *p = NULL when it fails
-  template <class T>
-  int alloc(T** p, size_t n, bool pinned = false) {  // n elements (at least one)
-    return alloc_bytes((void**)p, std::max<size_t>(n, 1) * sizeof(T), pinned);
-  }
-  size_t bytes_of(const void* p) const;  // 0: not a buffer of this owner
-  void release(void* p);
-  void release_all();
-};
 
 struct Lane {
   hipStream_t stream = nullptr;  // everything of a batch runs in this ONE in-order stream (no side streams: an error return leaves nothing to join)

@@ -20,7 +20,7 @@
 #include <climits>
 #include <cmath>
 
-#include "common.hpp"
+#include "devmem.hpp"
 #include "fundamental.hpp"
 
 namespace uvo {
@@ -551,17 +551,11 @@ __global__ __launch_bounds__(64) void k_fm_replay(FmReplay a) {
   }
 }
 
-int fm_alloc(FmScratch& f) {
-  const size_t o_sub = 64, o_end = o_sub + kFmCap * 7 * 4, o_nm = o_end + kFmCap * 4, o_mod = (o_nm + kFmCap * 4 + 63) & ~(size_t)63,
-               o_sc = o_mod + (size_t)kFmCap * 27 * 8, o_jump = o_sc + kFmCap * 3 * 8, bytes = o_jump + kFmT * 8;
-  if (hipMalloc((void**)&f.block, bytes) != hipSuccess) return fail(UVO_E_NOMEM, "RANSAC scratch allocation failed");
-  f.state = reinterpret_cast<FmState*>(f.block);
-  f.subsets = reinterpret_cast<int32_t*>(f.block + o_sub);
-  f.hyp_end = reinterpret_cast<uint32_t*>(f.block + o_end);
-  f.nmodels = reinterpret_cast<int32_t*>(f.block + o_nm);
-  f.models = reinterpret_cast<double*>(f.block + o_mod);
-  f.scores = reinterpret_cast<double*>(f.block + o_sc);
-  f.jump = reinterpret_cast<uint64_t*>(f.block + o_jump);
+int fm_alloc(DevMem& m, FmScratch& f) {
+  RC(alloc_carved(m, [&](Carve& c) {
+    c.take(f.state, 1, 64).take(f.subsets, kFmCap * 7, 64).take(f.hyp_end, kFmCap, alignof(uint32_t)).take(f.nmodels, kFmCap, alignof(int32_t));
+    c.take(f.models, kFmCap * 27, 64).take(f.scores, kFmCap * 3, alignof(double)).take(f.jump, kFmT, alignof(uint64_t));
+  }));
   // lane t of k_fm_subsets starts kFmP * t draws into the window: A^(kFmP * t) mod M, with 128-bit host arithmetic
   uint64_t jump[kFmT];
   unsigned __int128 step = 1;
@@ -573,11 +567,6 @@ int fm_alloc(FmScratch& f) {
   }
   UVO_HIP_CHECK(hipMemcpy(f.jump, jump, sizeof jump, hipMemcpyHostToDevice));
   return UVO_OK;
-}
-
-void fm_free(FmScratch& f) {
-  if (f.block) (void)hipFree(f.block);
-  f = FmScratch();
 }
 
 int fm_fixup(double& thr, double& conf) {

@@ -7,9 +7,9 @@ namespace uvo {
 
 constexpr int kFmCap = 1000;  // hypotheses: maxIters of both estimators
 
+struct DevMem;
 struct FmState;
 struct FmScratch {              // one device block, sized at uvo_klt_create
-  uint8_t* block = nullptr;
   FmState* state = nullptr;
   int32_t* subsets = nullptr;   // [kFmCap][7]
   uint32_t* hyp_end = nullptr;  // [kFmCap] RNG draws consumed once hypothesis h is drawn
@@ -29,8 +29,7 @@ struct FmOut {
 };
 static_assert(sizeof(FmOut) == 128, "FmOut is 128 bytes");
 
-int fm_alloc(FmScratch& f);
-void fm_free(FmScratch& f);
+int fm_alloc(DevMem& m, FmScratch& f);  // from the handle's memory
 // OpenCV's parameter fix-ups (thr <= 0 -> 3, conf outside (DBL_EPSILON, 1 - DBL_EPSILON) -> 0.99); NaN is an argument error
 int fm_fixup(double& thr, double& conf);
 // n >= 7 point pairs d_p0 / d_p1 ([n][2] float); mask = inlier && d_status[i] (d_status NULL: inlier)

@@ -18,9 +18,10 @@
 //                       not a sum); then the verdict of ReconstructF and the result record, vP3D and vbTriangulated.
 #include <cmath>
 #include <cstring>
+#include <utility>
 #include <vector>
 
-#include "common.hpp"
+#include "devmem.hpp"
 #include "initializer.hpp"
 #include "pnpsolver.hpp"
 
@@ -248,10 +249,16 @@ struct uvo_initializer {
   uvo_klt* klt = nullptr;
   hipStream_t stream = nullptr;
   int device = 0, max_keys = 0, max_words = 0;
-  uint8_t *block = nullptr, *h_up = nullptr, *h_down = nullptr;
-  size_t up_bytes = 0, down_bytes = 0;
+  DevMem mem;  // owns D's block and the two mirrors
   InitDev D;
   float* keys1 = nullptr;  // writable view of D's
+  // page-locked mirrors of the two exchanges, and the arrays of the last initialize call in them (exchanges)
+  uint8_t *h_up = nullptr, *h_down = nullptr, *tri = nullptr;
+  InitCall* call = nullptr;
+  float *keys2 = nullptr, *p3d = nullptr;
+  int32_t *m12 = nullptr, *sets = nullptr;
+  InitOut* out = nullptr;
+  uint64_t* mask = nullptr;
   bool ready = false;      // set_reference has run
   int n1 = 0, iterations = 0, tap_n = 0;
   float sigma = 1.f;
@@ -260,15 +267,22 @@ struct uvo_initializer {
   std::vector<int32_t> avail;  // draw_set's slots
 };
 
+// The two exchanges of an initialize call of n2 keys and T sets, each one copy (the kernels find their side with call_of .. sets_of, and in
+// k_init_finish): places the call's arrays in the mirrors -- before there are any, at create, it only measures; -> bytes up, bytes down
+static std::pair<size_t, size_t> exchanges(uvo_initializer* s, size_t n2, size_t T) {
+  Carve u{s->h_up}, d{s->h_down};
+  u.take(s->call, 1).take(s->keys2, n2 * 2, alignof(float)).take(s->m12, n2, alignof(int32_t)).take(s->sets, T * twoview::kSet, alignof(int32_t));
+  d.take(s->out, 1).take(s->mask, (n2 + 63) / 64, alignof(uint64_t)).take(s->p3d, n2 * 3, alignof(float)).take(s->tri, n2, 1);
+  return {u.off, d.off};
+}
+
 extern "C" {
 
 void uvo_initializer_destroy(uvo_initializer* s) {
   if (!s) return;
   hipSetDevice(s->device);
   if (s->stream) hipStreamSynchronize(s->stream);
-  if (s->block) (void)hipFree(s->block);
-  if (s->h_up) (void)hipHostFree(s->h_up);
-  if (s->h_down) (void)hipHostFree(s->h_down);
+  s->mem.release_all();
   delete s;
 }
 
@@ -280,24 +294,18 @@ int uvo_initializer_create(uvo_klt* k, int max_keys, uvo_initializer** out) {
   s->klt = k, s->stream = klt_stream(k), s->device = klt_device(k);
   s->max_keys = max_keys, s->max_words = (max_keys + 63) / 64;
   const size_t N = (size_t)max_keys, W = (size_t)s->max_words, T = (size_t)kInitMaxIterations;
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  s->up_bytes = sizeof(InitCall) + N * 8 + N * 4 + T * twoview::kSet * 4;
-  s->down_bytes = sizeof(InitOut) + W * 8 + N * 12 + N;
-  const size_t o_k1 = 0, o_up = up(o_k1 + N * 8), o_F = up(o_up + s->up_bytes), o_sc = up(o_F + T * 36), o_mask = up(o_sc + T * 4), o_sel = up(o_mask + T * W * 8),
-               o_fl = up(o_sel + sizeof(InitSel)), o_cos = up(o_fl + 4 * N), o_p3d = up(o_cos + 16 * N), o_down = up(o_p3d + 48 * N), bytes = o_down + s->down_bytes;
-  if (hipSetDevice(s->device) != hipSuccess || hipMalloc((void**)&s->block, bytes) != hipSuccess ||
-      hipHostMalloc((void**)&s->h_up, s->up_bytes, hipHostMallocDefault) != hipSuccess ||
-      hipHostMalloc((void**)&s->h_down, s->down_bytes, hipHostMallocDefault) != hipSuccess) {
-    uvo_initializer_destroy(s);
-    return fail(UVO_E_NOMEM, "Initializer allocation failed");
-  }
-  uint8_t* b = s->block;
-  s->keys1 = reinterpret_cast<float*>(b + o_k1);
+  const auto [up_bytes, down_bytes] = exchanges(s, N, T);
   InitDev& D = s->D;
   D.max_keys = max_keys, D.max_words = s->max_words;
-  D.keys1 = s->keys1, D.up = b + o_up, D.F = reinterpret_cast<float*>(b + o_F), D.scores = reinterpret_cast<float*>(b + o_sc);
-  D.masks = reinterpret_cast<uint64_t*>(b + o_mask), D.sel = reinterpret_cast<InitSel*>(b + o_sel), D.flags = b + o_fl;
-  D.cosp = reinterpret_cast<float*>(b + o_cos), D.p3d = reinterpret_cast<float*>(b + o_p3d), D.down = b + o_down;
+  int rc = hipSetDevice(s->device) == hipSuccess ? UVO_OK : fail(UVO_E_NOMEM, "Initializer allocation failed");
+  if (!rc) rc = alloc_carved(s->mem, [&, up = up_bytes, down = down_bytes](Carve& c) {
+    c.take(s->keys1, N * 2).take(D.up, up).take(D.F, T * 9).take(D.scores, T).take(D.masks, T * W).take(D.sel, 1);
+    c.take(D.flags, 4 * N).take(D.cosp, 4 * N).take(D.p3d, 4 * N * 3).take(D.down, down);
+  });
+  if (!rc) rc = s->mem.alloc(&s->h_up, up_bytes, true);
+  if (!rc) rc = s->mem.alloc(&s->h_down, down_bytes, true);
+  if (rc) return uvo_initializer_destroy(s), rc;
+  D.keys1 = s->keys1;
   s->avail.resize(N);
   *out = s;
   return UVO_OK;
@@ -338,21 +346,17 @@ int uvo_initializer_initialize(uvo_initializer* s, const float* keys2_xy, int n2
     return UVO_OK;
   }
   const int T = s->iterations, words = (n2 + 63) / 64;
-  InitCall* call = reinterpret_cast<InitCall*>(s->h_up);
+  const auto [up_bytes, down_bytes] = exchanges(s, (size_t)n2, (size_t)T);
+  InitCall* call = s->call;
   std::memset(call, 0, sizeof *call);
   call->n1 = s->n1, call->n2 = n2, call->T = T, call->words = words;
   call->N1 = s->N1, call->N2 = twoview::normalize(keys2_xy, n2), call->K = s->K;
   call->inv_sigma2 = twoview::inv_sigma_square(s->sigma), call->th2 = twoview::th2_of(s->sigma);
-  float* k2 = reinterpret_cast<float*>(s->h_up + sizeof(InitCall));
-  int32_t* m12 = reinterpret_cast<int32_t*>(k2 + 2 * (size_t)n2);
-  int32_t* sets = m12 + n2;
-  std::memcpy(k2, keys2_xy, (size_t)n2 * 8);
-  std::memcpy(m12, matches12, (size_t)n2 * 4);
+  std::memcpy(s->keys2, keys2_xy, (size_t)n2 * 8);
+  std::memcpy(s->m12, matches12, (size_t)n2 * 4);
   pnps::GlibcRand g;
   std::memcpy(&g, rng, sizeof g);
-  for (int it = 0; it < T; ++it) twoview::draw_set(g, n2, s->avail.data(), sets + (size_t)it * twoview::kSet);
-  const size_t up_bytes = sizeof(InitCall) + (size_t)n2 * 12 + (size_t)T * twoview::kSet * 4;
-  const size_t down_bytes = sizeof(InitOut) + (size_t)words * 8 + (size_t)n2 * 13;
+  for (int it = 0; it < T; ++it) twoview::draw_set(g, n2, s->avail.data(), s->sets + (size_t)it * twoview::kSet);
   UVO_HIP_CHECK(hipSetDevice(s->device));
   hipStream_t st = s->stream;
   UVO_HIP_CHECK(hipMemcpyAsync(const_cast<uint8_t*>(s->D.up), s->h_up, up_bytes, hipMemcpyHostToDevice, st));
@@ -365,19 +369,17 @@ int uvo_initializer_initialize(uvo_initializer* s, const float* keys2_xy, int n2
   UVO_HIP_CHECK(hipMemcpyAsync(s->h_down, s->D.down, down_bytes, hipMemcpyDeviceToHost, st));
   UVO_HIP_CHECK(hipStreamSynchronize(st));
   s->tap_n = T;
-  const InitOut& o = *reinterpret_cast<const InitOut*>(s->h_down);
+  const InitOut& o = *s->out;
   result->initialized = o.ok, result->best = o.best, result->n_inliers = o.n_inliers, result->deciding = o.deciding, result->score = o.score;
   std::memcpy(result->n_good, o.n_good, 16);
   std::memcpy(result->parallax, o.parallax, 16);
   std::memcpy(result->R21, o.R, 36);
   std::memcpy(result->t21, o.t, 12);
   std::memcpy(result->F21, o.F, 36);
-  const uint64_t* mw = reinterpret_cast<const uint64_t*>(s->h_down + sizeof(InitOut));
   if (inl)
-    for (int i = 0; i < n2; ++i) inl[i] = (uint8_t)(mw[i >> 6] >> (i & 63) & 1);
-  const uint8_t* dp = s->h_down + sizeof(InitOut) + (size_t)words * 8;
-  if (p3d) std::memcpy(p3d, dp, (size_t)n2 * 12);
-  if (tri) std::memcpy(tri, dp + (size_t)n2 * 12, (size_t)n2);
+    for (int i = 0; i < n2; ++i) inl[i] = (uint8_t)(s->mask[i >> 6] >> (i & 63) & 1);
+  if (p3d) std::memcpy(p3d, s->p3d, (size_t)n2 * 12);
+  if (tri) std::memcpy(tri, s->tri, (size_t)n2);
   result->draws = (uint32_t)(T * twoview::kSet);
   std::memcpy(rng, &g, sizeof g);  // the caller's state stands where rand() would after the 8 * iterations draws
   return UVO_OK;
@@ -390,9 +392,7 @@ int uvo_initializer_hypotheses(uvo_initializer* s, int32_t* subsets, float* F, f
   if (m > 0 && (!subsets || !F || !scores)) return fail(UVO_E_BADARG, "null pointer");
   *n = m;
   if (m == 0) return UVO_OK;
-  const InitCall* call = reinterpret_cast<const InitCall*>(s->h_up);  // the sets were drawn on the host
-  const int32_t* sets = reinterpret_cast<const int32_t*>(s->h_up + sizeof(InitCall) + (size_t)call->n2 * 12);
-  std::memcpy(subsets, sets, (size_t)m * twoview::kSet * 4);
+  std::memcpy(subsets, s->sets, (size_t)m * twoview::kSet * 4);  // drawn on the host in the last call
   UVO_HIP_CHECK(hipSetDevice(s->device));
   UVO_HIP_CHECK(hipMemcpy(F, s->D.F, (size_t)m * 36, hipMemcpyDeviceToHost));
   UVO_HIP_CHECK(hipMemcpy(scores, s->D.scores, (size_t)m * 4, hipMemcpyDeviceToHost));

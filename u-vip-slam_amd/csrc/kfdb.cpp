@@ -8,6 +8,7 @@
 #include <unordered_set>
 #include <vector>
 
+#include "devmem.hpp"
 #include "kfdb.hpp"
 #include "kfdb_core.hpp"
 
@@ -17,6 +18,7 @@ struct uvo_kfdb {
   int device = 0, max_kf = 0, max_words = 0, hash_len = 0, npad = 0;
   int n_slots = 0;
   hipStream_t stream = nullptr;
+  DevMem mem;  // owns every d_* and the pinned block of the h_*
   // device, per slot
   uint32_t* d_seq = nullptr;
   int32_t *d_slot_of_seq = nullptr, *d_kf_n = nullptr, *d_cov = nullptr;
@@ -32,7 +34,6 @@ struct uvo_kfdb {
   uint64_t* d_keys = nullptr;
   uvo_kfdb_query_row* d_rows = nullptr;
   // pinned host: mirrors, staging, results
-  uint8_t* h_block = nullptr;
   int64_t* h_id = nullptr;
   uint32_t* h_seq = nullptr;
   int32_t *h_slot_of_seq = nullptr, *h_kf_n = nullptr, *h_cov = nullptr, *h_out = nullptr;
@@ -135,11 +136,7 @@ void uvo_kfdb_destroy(uvo_kfdb* db) {
   if (!db) return;
   hipSetDevice(db->device);
   if (db->stream) hipStreamSynchronize(db->stream);
-  void* ptrs[] = {db->d_seq,   db->d_slot_of_seq, db->d_kf_n,  db->d_cov,     db->d_in_file, db->d_has_hash, db->d_bow_id, db->d_bow_val, db->d_hash_t,
-                  db->d_state, db->d_stage, db->d_cnt,         db->d_first, db->d_first_r, db->d_out,     db->d_score,    db->d_hm,     db->d_keys,    db->d_rows};
-  for (void* p : ptrs)
-    if (p) hipFree(p);
-  if (db->h_block) hipHostFree(db->h_block);
+  db->mem.release_all();
   if (db->stream) hipStreamDestroy(db->stream);
   delete db;
 }
@@ -161,29 +158,34 @@ int uvo_kfdb_create(int max_keyframes, int max_words, int hash_len, int device, 
   const size_t K = (size_t)max_keyframes, W = (size_t)max_words, H = (size_t)hash_len, C = kfdb::kCovisibles;
   // staging: a BoW query (values, ids, connected flags) or a haloc query (hash, skip flags)
   db->stage_bytes = std::max(up16(W * 12) + K, up16(H * 4) + K) + 16;
-  int rc;
-  if ((rc = dev_malloc((void**)&db->d_seq, K * 4)) || (rc = dev_malloc((void**)&db->d_slot_of_seq, K * 4)) ||
-      (rc = dev_malloc((void**)&db->d_kf_n, K * 4)) || (rc = dev_malloc((void**)&db->d_cov, K * C * 4)) || (rc = dev_malloc((void**)&db->d_in_file, K)) ||
-      (rc = dev_malloc((void**)&db->d_has_hash, K)) || (rc = dev_malloc((void**)&db->d_bow_id, K * W * 4)) || (rc = dev_malloc((void**)&db->d_bow_val, K * W * 8)) ||
-      (rc = dev_malloc((void**)&db->d_hash_t, K * H * 4)) || (rc = dev_malloc((void**)&db->d_state, K * sizeof(uvo_kfdb_fields))) ||
-      (rc = dev_malloc((void**)&db->d_stage, db->stage_bytes)) || (rc = dev_malloc((void**)&db->d_cnt, K * 4)) || (rc = dev_malloc((void**)&db->d_first, K * 4)) ||
-      (rc = dev_malloc((void**)&db->d_first_r, K * 4)) || (rc = dev_malloc((void**)&db->d_out, (kKfdbMeta + std::max(K, (size_t)3)) * 4)) || (rc = dev_malloc((void**)&db->d_score, K * 4)) ||
-      (rc = dev_malloc((void**)&db->d_hm, K * 4)) || (rc = dev_malloc((void**)&db->d_keys, (size_t)db->npad * 8)) ||
-      (rc = dev_malloc((void**)&db->d_rows, K * sizeof(uvo_kfdb_query_row)))) {
-    uvo_kfdb_destroy(db);
-    return rc;
-  }
-  // one pinned block: id | seq | slot_of_seq | kf_n | cov | out | in_file | has_hash | stage
-  const size_t o_id = 0, o_seq = o_id + up16(K * 8), o_sos = o_seq + up16(K * 4), o_n = o_sos + up16(K * 4), o_cov = o_n + up16(K * 4), o_out = o_cov + up16(K * C * 4),
-               o_in = o_out + up16((kKfdbMeta + std::max(K, (size_t)3)) * 4), o_hh = o_in + up16(K), o_st = o_hh + up16(K), total = o_st + db->stage_bytes;
-  if (hipHostMalloc((void**)&db->h_block, total) != hipSuccess) {
-    db->h_block = nullptr;
-    uvo_kfdb_destroy(db);
-    return fail(UVO_E_NOMEM, "pinned host allocation failed");
-  }
-  uint8_t* b = db->h_block;
-  db->h_id = (int64_t*)(b + o_id), db->h_seq = (uint32_t*)(b + o_seq), db->h_slot_of_seq = (int32_t*)(b + o_sos), db->h_kf_n = (int32_t*)(b + o_n);
-  db->h_cov = (int32_t*)(b + o_cov), db->h_out = (int32_t*)(b + o_out), db->h_in_file = b + o_in, db->h_has_hash = b + o_hh, db->h_stage = b + o_st;
+  const size_t n_out = kKfdbMeta + std::max(K, (size_t)3);
+  auto alloc_all = [&, &m = db->mem]() {
+    RC(m.alloc(&db->d_seq, K));
+    RC(m.alloc(&db->d_slot_of_seq, K));
+    RC(m.alloc(&db->d_kf_n, K));
+    RC(m.alloc(&db->d_cov, K * C));
+    RC(m.alloc(&db->d_in_file, K));
+    RC(m.alloc(&db->d_has_hash, K));
+    RC(m.alloc(&db->d_bow_id, K * W));
+    RC(m.alloc(&db->d_bow_val, K * W));
+    RC(m.alloc(&db->d_hash_t, K * H));
+    RC(m.alloc(&db->d_state, K));
+    RC(m.alloc(&db->d_stage, db->stage_bytes));
+    RC(m.alloc(&db->d_cnt, K));
+    RC(m.alloc(&db->d_first, K));
+    RC(m.alloc(&db->d_first_r, K));
+    RC(m.alloc(&db->d_out, n_out));
+    RC(m.alloc(&db->d_score, K));
+    RC(m.alloc(&db->d_hm, K));
+    RC(m.alloc(&db->d_keys, (size_t)db->npad));
+    RC(m.alloc(&db->d_rows, K));
+    // one pinned block: mirrors, results, staging
+    return alloc_carved(m, [&](Carve& c) {
+      c.take(db->h_id, K, 16).take(db->h_seq, K, 16).take(db->h_slot_of_seq, K, 16).take(db->h_kf_n, K, 16).take(db->h_cov, K * C, 16);
+      c.take(db->h_out, n_out, 16).take(db->h_in_file, K, 16).take(db->h_has_hash, K, 16).take(db->h_stage, db->stage_bytes, 16);
+    }, true);
+  };
+  if (const int rc = alloc_all()) return uvo_kfdb_destroy(db), rc;
   *out = db;
   return UVO_OK;
 }

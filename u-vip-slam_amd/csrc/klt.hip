@@ -282,6 +282,7 @@ struct uvo_klt {
   hipStream_t stream = nullptr;
   KltGeom geom;          // for the maximum image size: offsets fixed at create
   int64_t img_block = 0, der_block = 0;  // per slot
+  DevMem mem;                  // owns every d_* / h_* below, and the scratch of fm and pnp
   uint8_t* d_img = nullptr;    // [slots][img_block]
   int16_t* d_der = nullptr;    // [slots][der_block]
   uint8_t* d_in = nullptr;     // staging of the caller image
@@ -327,12 +328,7 @@ void uvo_klt_destroy(uvo_klt* k) {
   if (!k) return;
   hipSetDevice(k->cfg.device);
   if (k->stream) hipStreamSynchronize(k->stream);
-  void* ptrs[] = {k->d_img, k->d_der, k->d_in, k->d_pts};
-  for (void* p : ptrs)
-    if (p) hipFree(p);
-  fm_free(k->fm);
-  pnp_free(k->pnp);
-  if (k->h_pts) (void)hipHostFree(k->h_pts);
+  k->mem.release_all();
   if (k->stream) hipStreamDestroy(k->stream);
   delete k;
 }
@@ -355,20 +351,15 @@ int uvo_klt_create(const uvo_klt_cfg* cfg, uvo_klt** out) {
   klt_geometry(cfg->max_width, cfg->max_height, cfg->win_width, cfg->win_height, cfg->max_level, k->geom, &k->img_block, &k->der_block);
   k->slot_w.assign(cfg->slots, 0), k->slot_h.assign(cfg->slots, 0), k->slot_levels.assign(cfg->slots, 0);
   const size_t S = (size_t)cfg->slots, N = (size_t)cfg->max_points;
-  if (hipMalloc((void**)&k->d_img, S * k->img_block) != hipSuccess || hipMalloc((void**)&k->d_der, S * k->der_block * 2) != hipSuccess ||
-      hipMalloc((void**)&k->d_in, (size_t)cfg->max_width * cfg->max_height) != hipSuccess || hipMalloc((void**)&k->d_pts, N * 40 + 320) != hipSuccess ||
-      hipHostMalloc((void**)&k->h_pts, N * 40 + 320, hipHostMallocDefault) != hipSuccess) {
-    uvo_klt_destroy(k);
-    return fail(UVO_E_NOMEM, "KLT scratch allocation failed");
-  }
-  if (const int rc = fm_alloc(k->fm)) {
-    uvo_klt_destroy(k);
-    return rc;
-  }
-  if (const int rc = pnp_alloc(k->pnp, cfg->max_points)) {
-    uvo_klt_destroy(k);
-    return rc;
-  }
+  DevMem& m = k->mem;
+  int rc = m.alloc(&k->d_img, S * k->img_block);
+  if (!rc) rc = m.alloc(&k->d_der, S * k->der_block);
+  if (!rc) rc = m.alloc(&k->d_in, (size_t)cfg->max_width * cfg->max_height);
+  if (!rc) rc = m.alloc(&k->d_pts, N * 40 + 320);
+  if (!rc) rc = m.alloc(&k->h_pts, N * 40 + 320, true);
+  if (!rc) rc = fm_alloc(m, k->fm);
+  if (!rc) rc = pnp_alloc(m, k->pnp, cfg->max_points);
+  if (rc) return uvo_klt_destroy(k), rc;
   *out = k;
   return UVO_OK;
 }

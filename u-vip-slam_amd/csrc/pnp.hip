@@ -18,7 +18,7 @@
 #include <cfloat>
 #include <cmath>
 
-#include "common.hpp"
+#include "devmem.hpp"
 #include "pnp.hpp"
 
 namespace uvo {
@@ -142,32 +142,13 @@ __global__ __launch_bounds__(256) void k_pnp_finish(pnp::Cam C, const float* __r
   }
 }
 
-int pnp_alloc(PnpScratch& p, int max_points) {
+int pnp_alloc(DevMem& m, PnpScratch& p, int max_points) {
   const size_t N = (size_t)max_points;
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t o_io = 0, o_uf = up(o_io + N * 20), o_ud = up(o_uf + N * 8), o_sub = up(o_ud + N * 16), o_end = up(o_sub + kFmCap * 5 * 4),
-               o_pose = up(o_end + kFmCap * 4), o_cnt = up(o_pose + (size_t)kFmCap * 12 * 8), o_out = up(o_cnt + kFmCap * 4),
-               bytes = o_out + sizeof(PnpOut) + N * 4;
-  if (hipMalloc((void**)&p.block, bytes) != hipSuccess || hipHostMalloc((void**)&p.h_io, N * 20 + sizeof(PnpOut), hipHostMallocDefault) != hipSuccess) {
-    pnp_free(p);
-    return fail(UVO_E_NOMEM, "PnP scratch allocation failed");
-  }
-  p.max_points = max_points;
-  p.io = reinterpret_cast<float*>(p.block + o_io);
-  p.und_f = reinterpret_cast<float*>(p.block + o_uf);
-  p.und_d = reinterpret_cast<double*>(p.block + o_ud);
-  p.subsets = reinterpret_cast<int32_t*>(p.block + o_sub);
-  p.hyp_end = reinterpret_cast<uint32_t*>(p.block + o_end);
-  p.poses = reinterpret_cast<double*>(p.block + o_pose);
-  p.counts = reinterpret_cast<int32_t*>(p.block + o_cnt);
-  p.out = reinterpret_cast<PnpOut*>(p.block + o_out);
-  return UVO_OK;
-}
-
-void pnp_free(PnpScratch& p) {
-  if (p.block) (void)hipFree(p.block);
-  if (p.h_io) (void)hipHostFree(p.h_io);
-  p = PnpScratch();
+  RC(alloc_carved(m, [&](Carve& c) {
+    c.take(p.io, N * 5).take(p.und_f, N * 2).take(p.und_d, N * 2).take(p.subsets, kFmCap * 5).take(p.hyp_end, kFmCap).take(p.poses, kFmCap * 12);
+    c.take(p.counts, kFmCap).take(p.out, 1).take(p.inliers, N, alignof(int32_t));
+  }));
+  return m.alloc(&p.h_io, N * 20 + sizeof(PnpOut), true);
 }
 
 int pnp_enqueue(hipStream_t s, const PnpScratch& p, int n, const pnp::Cam& cam, int iterations, double thr, double conf) {
@@ -180,7 +161,7 @@ int pnp_enqueue(hipStream_t s, const PnpScratch& p, int n, const pnp::Cam& cam, 
                      p.poses, p.counts);
   if (n != pnp::kModelPoints) hipLaunchKernelGGL(k_pnp_score, dim3(hyp), dim3(256), 0, s, cam, obj, img, n, t, p.poses, p.counts);
   hipLaunchKernelGGL(k_pnp_finish, dim3(1), dim3(256), 0, s, cam, obj, img, p.und_d, n, hyp, t, conf, p.subsets, p.hyp_end, p.poses, p.counts, p.out,
-                     reinterpret_cast<int32_t*>(p.out + 1));
+                     p.inliers);
   UVO_HIP_CHECK(hipGetLastError());
   return UVO_OK;
 }

@@ -20,7 +20,7 @@
 #include <cstring>
 #include <vector>
 
-#include "common.hpp"
+#include "devmem.hpp"
 #include "pnpsolver.hpp"
 
 namespace uvo {
@@ -196,10 +196,13 @@ struct uvo_pnpsolver_set {
   uvo_klt* klt = nullptr;
   hipStream_t stream = nullptr;
   int device = 0, max_solvers = 0, max_points = 0, words = 0, total = 0;
-  uint8_t *block = nullptr, *h_up = nullptr, *h_down = nullptr;
-  size_t up_bytes = 0, down_bytes = 0;
+  DevMem mem;  // owns D's block and the page-locked mirrors of its two exchanges
   PnpsDev D;
   float *p3d = nullptr, *p2d = nullptr, *max_err = nullptr;  // writable views of D's
+  PnpsCall* h_call = nullptr;  // the upload: call records, then hypothesis records
+  int32_t* h_hyp = nullptr;
+  PnpsResult* h_res = nullptr;  // the download: result records, then the returned sets
+  uint64_t* h_om = nullptr;
   std::vector<Solver> solvers;
   std::vector<int32_t> avail;  // draw_subset's slots
   std::vector<char> seen;      // per solver: listed in the current call
@@ -218,9 +221,7 @@ void uvo_pnpsolver_set_destroy(uvo_pnpsolver_set* s) {
   if (!s) return;
   hipSetDevice(s->device);
   if (s->stream) hipStreamSynchronize(s->stream);
-  if (s->block) (void)hipFree(s->block);
-  if (s->h_up) (void)hipHostFree(s->h_up);
-  if (s->h_down) (void)hipHostFree(s->h_down);
+  s->mem.release_all();
   delete s;
 }
 
@@ -233,28 +234,22 @@ int uvo_pnpsolver_set_create(uvo_klt* k, int max_solvers, int max_points, uvo_pn
   s->klt = k, s->stream = klt_stream(k), s->device = klt_device(k);
   s->max_solvers = max_solvers, s->max_points = max_points, s->words = (max_points + 63) / 64, s->total = max_solvers * kPnpsHypPerSolver;
   const size_t S = (size_t)max_solvers, N = (size_t)max_points, W = (size_t)s->words, T = (size_t)s->total;
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t o_p3d = 0, o_p2d = up(o_p3d + S * N * 12), o_me = up(o_p2d + S * N * 8), o_bm = up(o_me + S * N * 4), o_bp = up(o_bm + S * 2 * W * 8),
-               o_call = up(o_bp + S * 2 * 96), o_hyp = o_call + S * sizeof(PnpsCall), o_pose = up(o_hyp + T * kPnpsSubsetStride * 4),
-               o_cnt = up(o_pose + T * 96), o_mask = up(o_cnt + T * 4), o_list = up(o_mask + T * W * 8), o_res = up(o_list + S * N * 4),
-               o_om = o_res + S * sizeof(PnpsResult), bytes = o_om + S * W * 8;
-  s->up_bytes = S * sizeof(PnpsCall) + T * kPnpsSubsetStride * 4;  // call records and hypothesis records are adjacent: one copy
-  s->down_bytes = S * sizeof(PnpsResult) + S * W * 8;              // so are the result records and the returned sets
-  if (hipSetDevice(s->device) != hipSuccess || hipMalloc((void**)&s->block, bytes) != hipSuccess ||
-      hipHostMalloc((void**)&s->h_up, s->up_bytes, hipHostMallocDefault) != hipSuccess ||
-      hipHostMalloc((void**)&s->h_down, s->down_bytes, hipHostMallocDefault) != hipSuccess) {
-    uvo_pnpsolver_set_destroy(s);
-    return fail(UVO_E_NOMEM, "PnPsolver set allocation failed");
-  }
-  uint8_t* b = s->block;
-  s->p3d = reinterpret_cast<float*>(b + o_p3d), s->p2d = reinterpret_cast<float*>(b + o_p2d), s->max_err = reinterpret_cast<float*>(b + o_me);
   PnpsDev& D = s->D;
   D.max_points = max_points, D.words = s->words;
+  // each exchange is one copy: its two arrays are adjacent, on the device and in the mirror
+  auto upload = [&](Carve& c, auto*& call, auto*& hyp) { c.take(call, S).take(hyp, T * kPnpsSubsetStride, alignof(int32_t)); };
+  auto download = [&](Carve& c, auto*& res, auto*& om) { c.take(res, S).take(om, S * W, alignof(uint64_t)); };
+  int rc = hipSetDevice(s->device) == hipSuccess ? UVO_OK : fail(UVO_E_NOMEM, "PnPsolver set allocation failed");
+  if (!rc) rc = alloc_carved(s->mem, [&](Carve& c) {
+    c.take(s->p3d, S * N * 3).take(s->p2d, S * N * 2).take(s->max_err, S * N).take(D.best_mask, S * 2 * W).take(D.best_pose, S * 2 * 12);
+    upload(c, D.call, D.hyp);
+    c.take(D.poses, T * 12).take(D.counts, T).take(D.masks, T * W).take(D.list, S * N);
+    download(c, D.result, D.out_mask);
+  });
+  if (!rc) rc = alloc_carved(s->mem, [&](Carve& c) { upload(c, s->h_call, s->h_hyp); }, true);
+  if (!rc) rc = alloc_carved(s->mem, [&](Carve& c) { download(c, s->h_res, s->h_om); }, true);
+  if (rc) return uvo_pnpsolver_set_destroy(s), rc;
   D.p3d = s->p3d, D.p2d = s->p2d, D.max_err = s->max_err;
-  D.best_mask = reinterpret_cast<uint64_t*>(b + o_bm), D.best_pose = reinterpret_cast<double*>(b + o_bp);
-  D.call = reinterpret_cast<const PnpsCall*>(b + o_call), D.hyp = reinterpret_cast<const int32_t*>(b + o_hyp);
-  D.poses = reinterpret_cast<double*>(b + o_pose), D.counts = reinterpret_cast<int32_t*>(b + o_cnt), D.masks = reinterpret_cast<uint64_t*>(b + o_mask);
-  D.list = reinterpret_cast<int32_t*>(b + o_list), D.result = reinterpret_cast<PnpsResult*>(b + o_res), D.out_mask = reinterpret_cast<uint64_t*>(b + o_om);
   s->avail.resize(N);
   s->seen.resize(S);
   s->solvers.reserve(S);
@@ -336,8 +331,8 @@ int uvo_pnpsolver_iterate(uvo_pnpsolver_set* s, const int32_t* ids, int n_ids, i
   // solvers in front of it run
   pnps::GlibcRand g;
   std::memcpy(&g, rng, sizeof g);
-  PnpsCall* call = reinterpret_cast<PnpsCall*>(s->h_up);
-  int32_t* hyp = reinterpret_cast<int32_t*>(s->h_up + (size_t)s->max_solvers * sizeof(PnpsCall));
+  PnpsCall* call = s->h_call;
+  int32_t* hyp = s->h_hyp;
   int total = 0;
   for (int j = 0; j < n_ids; ++j) {
     const Solver& v = s->solvers[ids[j]];
@@ -353,19 +348,19 @@ int uvo_pnpsolver_iterate(uvo_pnpsolver_set* s, const int32_t* ids, int n_ids, i
     }
     total += K;
   }
-  const PnpsResult* res = reinterpret_cast<const PnpsResult*>(s->h_down);
+  const PnpsResult* res = s->h_res;
   const size_t W = (size_t)s->words;
   if (total > 0) {
     UVO_HIP_CHECK(hipSetDevice(s->device));
     hipStream_t st = s->stream;
-    UVO_HIP_CHECK(hipMemcpyAsync(const_cast<PnpsCall*>(s->D.call), s->h_up, (size_t)s->max_solvers * sizeof(PnpsCall) + (size_t)total * kPnpsSubsetStride * 4,
+    UVO_HIP_CHECK(hipMemcpyAsync(const_cast<PnpsCall*>(s->D.call), call, (size_t)s->max_solvers * sizeof(PnpsCall) + (size_t)total * kPnpsSubsetStride * 4,
                                  hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_pnps_hypotheses, dim3((total + kPnpsHypLanes - 1) / kPnpsHypLanes), dim3(kPnpsHypLanes), 0, st, s->D, total);
     hipLaunchKernelGGL(k_pnps_score, dim3(total), dim3(256), 0, st, s->D);
     hipLaunchKernelGGL(k_pnps_finish, dim3(n_ids), dim3(256), 0, st, s->D);
     UVO_HIP_CHECK(hipGetLastError());
     // result records of all solver slots, then the sets of the listed ones: adjacent on the device
-    UVO_HIP_CHECK(hipMemcpyAsync(s->h_down, s->D.result, (size_t)s->max_solvers * sizeof(PnpsResult) + (size_t)n_ids * W * 8, hipMemcpyDeviceToHost, st));
+    UVO_HIP_CHECK(hipMemcpyAsync(s->h_res, s->D.result, (size_t)s->max_solvers * sizeof(PnpsResult) + (size_t)n_ids * W * 8, hipMemcpyDeviceToHost, st));
     UVO_HIP_CHECK(hipStreamSynchronize(st));
   }
   int draws = 0;
@@ -390,7 +385,7 @@ int uvo_pnpsolver_iterate(uvo_pnpsolver_set* s, const int32_t* ids, int n_ids, i
     T[15] = 1.f;
     if (mask_out) {
       std::fill(mask_out, mask_out + v.n_matches, (uint8_t)0);
-      const uint64_t* words = reinterpret_cast<const uint64_t*>(s->h_down + (size_t)s->max_solvers * sizeof(PnpsResult)) + (size_t)j * W;
+      const uint64_t* words = s->h_om + (size_t)j * W;
       for (int i = 0; i < v.n; ++i)
         if (words[i >> 6] >> (i & 63) & 1) mask_out[v.kp_index[i]] = 1;
     }
@@ -411,7 +406,7 @@ int uvo_pnpsolver_hypotheses(uvo_pnpsolver_set* s, int id, int32_t* subsets, dou
   if (m > 0 && (!subsets || !poses || !counts)) return fail(UVO_E_BADARG, "null pointer");
   *n = m;
   if (m == 0) return UVO_OK;
-  const int32_t* hyp = reinterpret_cast<const int32_t*>(s->h_up + (size_t)s->max_solvers * sizeof(PnpsCall));  // the subsets were drawn on the host
+  const int32_t* hyp = s->h_hyp;  // the subsets were drawn on the host
   for (int h = 0; h < m; ++h)
     for (int e = 0; e < v.params.min_set; ++e) subsets[h * v.params.min_set + e] = hyp[(size_t)(v.tap_off + h) * kPnpsSubsetStride + 1 + e];
   UVO_HIP_CHECK(hipSetDevice(s->device));

@@ -37,6 +37,7 @@ struct Shard {
   int device = UVO_SHARD_REMOTE;
   uvo_extractor* ex = nullptr;
   uvo_matcher* mt = nullptr;
+  DevMem mem;  // owns the d_* rows
   // per pipeline lane: knn-2 rows of the chunk in HBM, and the events that order the two handles' streams
   int32_t *d_idx0[2] = {nullptr, nullptr}, *d_idx1[2] = {nullptr, nullptr};
   uint16_t *d_d0[2] = {nullptr, nullptr}, *d_d1[2] = {nullptr, nullptr};
@@ -114,10 +115,8 @@ void uvo_sharder_destroy(uvo_sharder* s) {
     (void)hipSetDevice(sh.device);
     if (sh.ex) (void)uvo_extractor_synchronize(sh.ex);
     if (sh.mt) (void)uvo_matcher_synchronize(sh.mt);
+    sh.mem.release_all();
     for (int l = 0; l < 2; ++l) {
-      void* p[] = {sh.d_idx0[l], sh.d_idx1[l], sh.d_d0[l], sh.d_d1[l]};
-      for (void* q : p)
-        if (q) (void)hipFree(q);
       if (sh.kernels_done[l]) (void)hipEventDestroy(sh.kernels_done[l]);
       if (sh.rows_sent[l]) (void)hipEventDestroy(sh.rows_sent[l]);
     }
@@ -166,16 +165,17 @@ int uvo_sharder_create(const uvo_sharder_cfg* cfg, uvo_sharder** out) {
         return rc;
       }
       const size_t rows = (size_t)cfg->chunk_frames * dcap;
-      bool ok = true;
-      for (int l = 0; l < 2 && ok; ++l) {
-        ok = hipMalloc((void**)&sh.d_idx0[l], rows * 4) == hipSuccess && hipMalloc((void**)&sh.d_idx1[l], rows * 4) == hipSuccess &&
-             hipMalloc((void**)&sh.d_d0[l], rows * 2) == hipSuccess && hipMalloc((void**)&sh.d_d1[l], rows * 2) == hipSuccess &&
-             hipEventCreateWithFlags(&sh.kernels_done[l], hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&sh.rows_sent[l], hipEventDisableTiming) == hipSuccess;
+      for (int l = 0; l < 2 && !rc; ++l) {
+        if ((rc = sh.mem.alloc(&sh.d_idx0[l], rows)) || (rc = sh.mem.alloc(&sh.d_idx1[l], rows)) || (rc = sh.mem.alloc(&sh.d_d0[l], rows)) ||
+            (rc = sh.mem.alloc(&sh.d_d1[l], rows)))
+          break;
+        if (hipEventCreateWithFlags(&sh.kernels_done[l], hipEventDisableTiming) != hipSuccess ||
+            hipEventCreateWithFlags(&sh.rows_sent[l], hipEventDisableTiming) != hipSuccess)
+          rc = fail(UVO_E_NOMEM, "sharder staging allocation failed");
       }
-      if (!ok) {
+      if (rc) {
         uvo_sharder_destroy(s);
-        return fail(UVO_E_NOMEM, "sharder staging allocation failed");
+        return rc;
       }
     }
   }

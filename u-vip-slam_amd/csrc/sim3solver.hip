@@ -17,6 +17,7 @@
 #include <cstring>
 #include <vector>
 
+#include "devmem.hpp"
 #include "matcher_priv.hpp"
 #include "sim3solver.hpp"
 
@@ -147,10 +148,13 @@ int max_its_of(int n, const sim3::Params& p) { return n >= sim3::kMinSet ? sim3:
 struct uvo_sim3solver_set {
   uvo_matcher* m = nullptr;
   int max_solvers = 0, max_points = 0, words = 0, total = 0;
-  uint8_t *block = nullptr, *h_up = nullptr, *h_down = nullptr;
-  size_t up_bytes = 0, down_bytes = 0;
+  DevMem mem;  // owns D's block and the page-locked mirrors of its two exchanges
   Sim3Dev D;
   float *x1c = nullptr, *x2c = nullptr, *p1 = nullptr, *p2 = nullptr, *e1 = nullptr, *e2 = nullptr;  // writable views of D's
+  Sim3Call* h_call = nullptr;  // the upload: call records, then subset records
+  int32_t* h_sub = nullptr;
+  Sim3Result* h_res = nullptr;  // the download: result records, then the returned sets
+  uint64_t* h_om = nullptr;
   std::vector<Solver> solvers;
   std::vector<int32_t> avail;  // draw_subset's slots
   std::vector<char> seen;      // per solver: listed in the current call
@@ -162,9 +166,7 @@ void uvo_sim3solver_set_destroy(uvo_sim3solver_set* s) {
   if (!s) return;
   hipSetDevice(s->m->device);
   if (s->m->stream) hipStreamSynchronize(s->m->stream);
-  if (s->block) (void)hipFree(s->block);
-  if (s->h_up) (void)hipHostFree(s->h_up);
-  if (s->h_down) (void)hipHostFree(s->h_down);
+  s->mem.release_all();
   delete s;
 }
 
@@ -177,28 +179,22 @@ int uvo_sim3solver_set_create(uvo_matcher* m, int max_solvers, int max_points, u
   s->m = m;
   s->max_solvers = max_solvers, s->max_points = max_points, s->words = (max_points + 63) / 64, s->total = max_solvers * kSim3HypPerSolver;
   const size_t S = (size_t)max_solvers, N = (size_t)max_points, W = (size_t)s->words, T = (size_t)s->total;
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t o_x1 = 0, o_x2 = up(o_x1 + S * N * 12), o_p1 = up(o_x2 + S * N * 12), o_p2 = up(o_p1 + S * N * 8), o_e1 = up(o_p2 + S * N * 8),
-               o_e2 = up(o_e1 + S * N * 4), o_call = up(o_e2 + S * N * 4), o_sub = o_call + S * sizeof(Sim3Call),
-               o_hyp = up(o_sub + T * kSim3SubsetStride * 4), o_cnt = up(o_hyp + T * kSim3HypFloats * 4), o_mask = up(o_cnt + T * 4),
-               o_res = up(o_mask + T * W * 8), o_om = o_res + S * sizeof(Sim3Result), bytes = o_om + S * W * 8;
-  s->up_bytes = S * sizeof(Sim3Call) + T * kSim3SubsetStride * 4;  // call records and subset records are adjacent: one copy
-  s->down_bytes = S * sizeof(Sim3Result) + S * W * 8;              // so are the result records and the returned sets
-  if (hipSetDevice(m->device) != hipSuccess || hipMalloc((void**)&s->block, bytes) != hipSuccess ||
-      hipHostMalloc((void**)&s->h_up, s->up_bytes, hipHostMallocDefault) != hipSuccess ||
-      hipHostMalloc((void**)&s->h_down, s->down_bytes, hipHostMallocDefault) != hipSuccess) {
-    uvo_sim3solver_set_destroy(s);
-    return fail(UVO_E_NOMEM, "Sim3Solver set allocation failed");
-  }
-  uint8_t* b = s->block;
-  auto fp = [&](size_t o) { return reinterpret_cast<float*>(b + o); };
-  s->x1c = fp(o_x1), s->x2c = fp(o_x2), s->p1 = fp(o_p1), s->p2 = fp(o_p2), s->e1 = fp(o_e1), s->e2 = fp(o_e2);
   Sim3Dev& D = s->D;
   D.max_points = max_points, D.words = s->words;
+  // each exchange is one copy: its two arrays are adjacent, on the device and in the mirror
+  auto upload = [&](Carve& c, auto*& call, auto*& sub) { c.take(call, S).take(sub, T * kSim3SubsetStride, alignof(int32_t)); };
+  auto download = [&](Carve& c, auto*& res, auto*& om) { c.take(res, S).take(om, S * W, alignof(uint64_t)); };
+  int rc = hipSetDevice(m->device) == hipSuccess ? UVO_OK : fail(UVO_E_NOMEM, "Sim3Solver set allocation failed");
+  if (!rc) rc = alloc_carved(s->mem, [&](Carve& c) {
+    c.take(s->x1c, S * N * 3).take(s->x2c, S * N * 3).take(s->p1, S * N * 2).take(s->p2, S * N * 2).take(s->e1, S * N).take(s->e2, S * N);
+    upload(c, D.call, D.sub);
+    c.take(D.hyp, T * kSim3HypFloats).take(D.counts, T).take(D.masks, T * W);
+    download(c, D.result, D.out_mask);
+  });
+  if (!rc) rc = alloc_carved(s->mem, [&](Carve& c) { upload(c, s->h_call, s->h_sub); }, true);
+  if (!rc) rc = alloc_carved(s->mem, [&](Carve& c) { download(c, s->h_res, s->h_om); }, true);
+  if (rc) return uvo_sim3solver_set_destroy(s), rc;
   D.x1c = s->x1c, D.x2c = s->x2c, D.p1 = s->p1, D.p2 = s->p2, D.e1 = s->e1, D.e2 = s->e2;
-  D.call = reinterpret_cast<const Sim3Call*>(b + o_call), D.sub = reinterpret_cast<const int32_t*>(b + o_sub);
-  D.hyp = fp(o_hyp), D.counts = reinterpret_cast<int32_t*>(b + o_cnt), D.masks = reinterpret_cast<uint64_t*>(b + o_mask);
-  D.result = reinterpret_cast<Sim3Result*>(b + o_res), D.out_mask = reinterpret_cast<uint64_t*>(b + o_om);
   s->avail.resize(N);
   s->seen.resize(S);
   s->solvers.reserve(S);
@@ -309,8 +305,8 @@ int uvo_sim3solver_iterate(uvo_sim3solver_set* s, const int32_t* ids, int n_ids,
   // which is the stream position in the only case in which solver k is reached
   pnps::GlibcRand g;
   std::memcpy(&g, rng, sizeof g);
-  Sim3Call* call = reinterpret_cast<Sim3Call*>(s->h_up);
-  int32_t* sub = reinterpret_cast<int32_t*>(s->h_up + (size_t)s->max_solvers * sizeof(Sim3Call));
+  Sim3Call* call = s->h_call;
+  int32_t* sub = s->h_sub;
   int total = 0;
   for (int j = 0; j < n_ids; ++j) {
     const Solver& v = s->solvers[ids[j]];
@@ -324,13 +320,13 @@ int uvo_sim3solver_iterate(uvo_sim3solver_set* s, const int32_t* ids, int n_ids,
     }
     total += K;
   }
-  const Sim3Result* res = reinterpret_cast<const Sim3Result*>(s->h_down);
+  const Sim3Result* res = s->h_res;
   const size_t W = (size_t)s->words;
   if (total > 0) {
     uvo_matcher* m = s->m;
     UVO_HIP_CHECK(hipSetDevice(m->device));
     hipStream_t st = m->stream;
-    UVO_HIP_CHECK(hipMemcpyAsync(const_cast<Sim3Call*>(s->D.call), s->h_up, (size_t)s->max_solvers * sizeof(Sim3Call) + (size_t)total * kSim3SubsetStride * 4,
+    UVO_HIP_CHECK(hipMemcpyAsync(const_cast<Sim3Call*>(s->D.call), call, (size_t)s->max_solvers * sizeof(Sim3Call) + (size_t)total * kSim3SubsetStride * 4,
                                  hipMemcpyHostToDevice, st));
     {
       Profiler::Scope ps(&m->prof, "k_sim3_hypotheses", st);
@@ -346,7 +342,7 @@ int uvo_sim3solver_iterate(uvo_sim3solver_set* s, const int32_t* ids, int n_ids,
     }
     UVO_HIP_CHECK(hipGetLastError());
     // result records of all solver slots, then the sets of the listed ones: adjacent on the device
-    UVO_HIP_CHECK(hipMemcpyAsync(s->h_down, s->D.result, (size_t)s->max_solvers * sizeof(Sim3Result) + (size_t)n_ids * W * 8, hipMemcpyDeviceToHost, st));
+    UVO_HIP_CHECK(hipMemcpyAsync(s->h_res, s->D.result, (size_t)s->max_solvers * sizeof(Sim3Result) + (size_t)n_ids * W * 8, hipMemcpyDeviceToHost, st));
     UVO_HIP_CHECK(hipStreamSynchronize(st));
   }
   int draws = 0;
@@ -370,7 +366,7 @@ int uvo_sim3solver_iterate(uvo_sim3solver_set* s, const int32_t* ids, int n_ids,
     result->scale = r.hyp[28];
     if (mask_out) {
       std::fill(mask_out, mask_out + v.n_matches, (uint8_t)0);
-      const uint64_t* words = reinterpret_cast<const uint64_t*>(s->h_down + (size_t)s->max_solvers * sizeof(Sim3Result)) + (size_t)j * W;
+      const uint64_t* words = s->h_om + (size_t)j * W;
       for (int i = 0; i < v.n; ++i)
         if (words[i >> 6] >> (i & 63) & 1) mask_out[v.index1[i]] = 1;
     }
@@ -398,7 +394,7 @@ int uvo_sim3solver_hypotheses(uvo_sim3solver_set* s, int id, int32_t* subsets, f
   if (m > 0 && (!subsets || !T12 || !T21 || !counts)) return fail(UVO_E_BADARG, "null pointer");
   *n = m;
   if (m == 0) return UVO_OK;
-  const int32_t* sub = reinterpret_cast<const int32_t*>(s->h_up + (size_t)s->max_solvers * sizeof(Sim3Call));  // the subsets were drawn on the host
+  const int32_t* sub = s->h_sub;  // the subsets were drawn on the host
   for (int h = 0; h < m; ++h)
     for (int e = 0; e < 3; ++e) subsets[h * 3 + e] = sub[(size_t)(v.tap_off + h) * kSim3SubsetStride + 1 + e];
   std::vector<float> hyp((size_t)m * kSim3HypFloats);
