@@ -94,11 +94,25 @@ int uvo_extractor_tables(const uvo_extractor* h, float* scale, float* inv_scale,
  * num_featsneeded): include/ORBextractor.h:56-58, src/ORBextractor.cc:849-961; call site src/Tracking.cc:946.
  *   img/width/height/stride : CV_8UC1 host image
  *   in_kp/n_in              : caller keypoints (reference: `keypoints` on entry); passed through level 0
- *                             with recomputed angle when full_detect == 0, dropped when full_detect != 0
+ *                             with recomputed angle when full_detect == 0, dropped when full_detect != 0.
+ *                             Accepted range (full_detect == 0): the centre (cvRound(x), cvRound(y)), halves to
+ *                             the even neighbour, lies in [2, width - 3] x [2, height - 3] -- the orientation
+ *                             patch (15 pixels) and the steered pattern (18) then stay inside the 16-pixel
+ *                             REFLECT_101 border, which the descriptor samples un-blurred as the reference
+ *                             does.  Any other centre: UVO_E_BADARG, nothing is written.  x and y come back
+ *                             as given, unrounded.
  *   grid2d                  : Eigen::MatrixXi::data() -- column-major int32, grid_rows x grid_cols,
  *                             read and MUTATED when full_detect == 0 (may be NULL when full_detect != 0)
+ *   num_feats_needed        : the reference's num_featsneeded (full_detect == 0), with its arithmetic: level l
+ *                             stops after num_feats_needed * (8 - l) / 30 accepted points (int division; the
+ *                             count carries over from levels that ran out of points first), the call after
+ *                             num_feats_needed.  Both tests are `==`, the level's first: 30 return 36.  At and
+ *                             below zero nothing is refused and no test can ever hold -- as for levels past
+ *                             the eighth -- so every detected point in a free cell is returned.
  *   out_kp/out_desc/cap     : caller buffers for up to `cap` keypoints (28 B) and descriptors (32 B)
  *   n_out                   : number of keypoints produced (reference: keypoints.size() on return)
+ * A cell of grid2d is free while it is <= 0 and is incremented per accepted point: a cell below zero takes
+ * more than one.
  * Keypoints come out level-major in the reference's list order; nothing is truncated to nfeatures.
  */
 int uvo_extract(uvo_extractor* h, const uint8_t* img, int width, int height, ptrdiff_t stride, const uvo_keypoint* in_kp, int n_in,

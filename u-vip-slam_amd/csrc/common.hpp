@@ -148,6 +148,8 @@ int launch_pyr_tiles(hipStream_t s, uint8_t* d_pyr, int64_t pyr_block, const Pyr
                      Level0View l0, int first, int last, int ntiles, uint32_t lds_bytes, int threads, int rows, int batch);
 void launch_gauss7(hipStream_t s, const uint8_t* d_pyr, uint8_t* d_blur, int64_t pyr_block, const LevelGeom* d_lv, const Geom& g, int4 taps,
                    int batch, int sse2_rounding, Level0View l0);
+// calls with caller keypoints only: level 0's un-blurred pad outside the blur's 4-pixel ring, padded plane -> tiled blurred plane (gauss.hip)
+void launch_blur_pad_level0(hipStream_t s, const uint8_t* d_pyr, uint8_t* d_blur, int64_t pyr_block, const LevelGeom& g0, int batch);
 void launch_fast_score(hipStream_t s, const LaneScratch& d, const Geom& g, int fast_th, int batch, Level0View l0);
 void launch_fast_cells(hipStream_t s, const LaneScratch& d, const Geom& g, const CellDesc* d_cells, const int32_t* d_flag_cell, int batch, Level0View l0);
 void launch_grider(hipStream_t s, const uint8_t* d_img, int w, int h, int64_t stride, int num_features, int grid_x, int grid_y, int threshold,

@@ -111,7 +111,21 @@ __global__ __launch_bounds__(256) void k_assemble(const LevelGeom* __restrict__ 
     s_lbase[nlevels] = run;
   }
   __syncthreads();
-  const bool staged = s_lbase[nlevels] <= AS_PTS && gsize <= AS_GRID;
+  // s_first[cell]: -1 = occupied, else the lowest index of a point of the current level that falls into the (free) cell
+  __shared__ int s_first[AS_GRID];
+  bool staged = s_lbase[nlevels] <= AS_PTS && gsize <= AS_GRID;
+  if (staged) {
+    // A cell below zero stays free (`> 0`, :888) for more than one point: it takes every point that falls into it until its count is
+    // positive, which the closed form below -- one point per free cell -- does not describe.  No caller builds such a grid
+    // (src/Tracking.cc:896-912 counts keypoints); one that holds a negative cell is walked sequentially like the large ones.
+    int below = 0;
+    for (int i = threadIdx.x; i < gsize; i += blockDim.x) {
+      const int v = Gm[i];
+      s_first[i] = v > 0 ? -1 : 0x7fffffff;
+      below |= v < 0;
+    }
+    staged = !__syncthreads_or(below);
+  }
   if (staged) {
     for (int l = 0; l < nlevels; ++l) {
       const int n = s_lbase[l + 1] - s_lbase[l];
@@ -127,12 +141,9 @@ __global__ __launch_bounds__(256) void k_assemble(const LevelGeom* __restrict__ 
     // the level, which has a closed form: the k-th accepted point has KP_counter = carry + k and Total_counter = total + k, the
     // loop breaks at the first k with carry + k == numofpoint (level cap, counter reset; checked first) or total + k == need
     // (global cap, break_key).
-    // s_first[cell]: -1 = occupied, else the lowest index of a point of the current level that falls into the (free) cell
-    __shared__ int s_first[AS_GRID];
     __shared__ int s_cell[AS_PTS];
     __shared__ int s_wcnt[4];
     const int tid = threadIdx.x, lane = tid & 63, wv = wave_in_block();
-    for (int i = tid; i < gsize; i += blockDim.x) s_first[i] = Gm[i] > 0 ? -1 : 0x7fffffff;
     __syncthreads();
     int pos = nin, Total_counter = 0, KP_counter = 0;
     bool break_key = false;

@@ -257,6 +257,13 @@ int run_batch_device(uvo_extractor* h, int li, const Batch& b) {
       if (rc) return rc;
     }
   }
+  if (have_in) {
+    // A caller keypoint may lie 2 pixels from the border of level 0 (validate(), extractor_host.cpp) and its steered pattern reaches 18:
+    // the blurred plane gets the un-blurred pad beyond the blur's ring, as the reference's in-place blur leaves it.  (Level 0 is the
+    // padded plane here: a call with caller keypoints never reads the image in place.)
+    ProfScope p(h, "k_blur_pad_level0");
+    launch_blur_pad_level0(s, L.d.pyr, L.d.blur, g.pyr_block, g.lv[0], batch);
+  }
   const bool direct = few && full_detect && !have_in;
   const FastAdapt fa{L.d.fcount, L.d.tpass, L.d.fstat, h->fast_mode == UVO_FAST_MODE_ADAPTIVE ? 1 : 0, h->cfg.fast_th};
   if (!direct) {

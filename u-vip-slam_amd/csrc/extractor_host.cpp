@@ -85,7 +85,8 @@ int validate(const uvo_extractor* h, const Batch& c, bool build_grid) {
   if ((!c.grid && !build_grid) || !c.nfn) return fail(UVO_E_BADARG, "top-up mode needs grid2d and num_feats_needed");
   if (!c.in_kp || !c.n_in) return UVO_OK;
   // the reference reads the centre pixel row of a caller keypoint without any bounds check; reject what would
-  // leave the padded plane (patch radius 15 + descriptor reach 18 against a 16 px pad)
+  // leave the padded plane (patch radius 15 + descriptor reach 18 against a 16 px pad).  The blurred plane holds that pad
+  // un-blurred out to 16 pixels on such calls (k_blur_pad_level0, gauss.hip).
   const int in_cap = h->cfg.max_input_keypoints;
   for (int b = 0; b < c.n; ++b) {
     if (c.n_in[b] < 0 || c.n_in[b] > in_cap) return fail(UVO_E_BADARG, "n_in outside 0..max_input_keypoints");
