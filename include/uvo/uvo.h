@@ -1023,6 +1023,80 @@ int uvo_pnpsolver_iterate(uvo_pnpsolver_set* s, const int32_t* ids, int n_ids, i
 int uvo_pnpsolver_hypotheses(uvo_pnpsolver_set* s, int id, int32_t* subsets, double* poses, int32_t* counts, int cap, int* n);
 
 /* ------------------------------------------------------------------------------------------------
+ * Pose-only optimisation -- replaces Optimizer::PoseOptimization(Frame*) (src/Optimizer.cc:2012-2145, the vision-only overload) and
+ * the parts of g2o it runs, as TrackWithPnP (:1884), TrackLocalMap (:1925), TrackwithMotionModel (:867) and Relocalisation (:2468,
+ * :2484, :2499) call it: one 6-DoF vertex, n fixed points, four rounds of Levenberg steps (its 10, 10, 7, 5; chi2 9.210, 7.378, 5.991,
+ * 5.991) with the Huber kernel at sqrt(5.991), the correspondences classified after every round.  ONE call optimises a list of
+ * independent problems: one upload, one launch (one workgroup per problem, all four rounds), one download, nothing allocated.
+ * The caller gathers each problem by walking mvpMapPoints as :2050-2096 does: for every index with a map point its world position,
+ * mvKeysUn[i].pt and mvInvLevelSigma2[octave].  Semantics are pinned to the reference's sources by tests/poseopt_model.py: the pose
+ * state is a unit quaternion and a translation in double, built from the float Tcw and normalised after every product; it is NOT
+ * reset between rounds; lambda, ni and the stall count are set anew in every round; an edge flagged in one round is judged again at
+ * the pose of every later round and comes back when its chi2 has fallen to the threshold; with n < 10 only the first round runs, with
+ * n >= 10 all four, however few correspondences are still active; there is no depth test.  Non-finite input is not rejected: it
+ * follows the arithmetic (a NaN chi2 satisfies neither test of the classification and leaves the flag as it was).
+ * Departures from the reference, all below what the float Tcw resolves on a well-posed problem:
+ *   - sums over the correspondences are reduced in a fixed tree over 256 lanes, not serially in index order;
+ *   - the 6 x 6 solve is an unpivoted LDL^T that fails unless every pivot is finite and > 0 (Eigen's LDLT pivots and accepts
+ *     semi-definite matrices); a failed solve makes the trial's chi2 DBL_MAX, as in the reference;
+ *   - sin and cos are the library's own (about 2^-51 absolute), pow(x, 3) is x * x * x; a step that rotates by more than 7 rad gives
+ *     a NaN pose for that trial, which is rejected like any other NaN trial.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct uvo_pose_optimizer uvo_pose_optimizer;
+
+typedef struct uvo_pose_problem {
+  const float* p3d;        /* [n][3] world positions of the map points */
+  const float* p2d;        /* [n][2] mvKeysUn[i].pt */
+  const float* inv_sigma2; /* [n]    mvInvLevelSigma2[mvKeysUn[i].octave] */
+  int32_t n;               /* 0..max_points */
+  float fx, fy, cx, cy;
+  float Tcw[16];           /* mTcw, row-major; only the upper 3 x 4 is read */
+  int32_t pad_;
+} uvo_pose_problem;
+
+typedef struct uvo_pose_result {
+  float Tcw[16];           /* the optimised pose rounded to float; with nothing to optimise the round trip of the input through a quaternion */
+  int32_t n_inliers;       /* nInitialCorrespondences - nBad of the last round run: the return value */
+  int32_t rounds;          /* 1 when n < 10, else 4 */
+  uint8_t* outlier;        /* caller's [n]: mvbOutlier of the problem's correspondences, in its order; may be NULL */
+  int32_t outlier_cap;     /* its length: UVO_E_CAPACITY when smaller than n */
+  int32_t pad_;
+} uvo_pose_result;
+
+/* test tap: what the Levenberg driver saw */
+typedef struct uvo_pose_trace_lin {
+  int32_t round, iteration;
+  double H[21];            /* upper triangle, row-major, before lambda */
+  double b[6];
+  double chi2;             /* activeRobustChi2 at the linearisation */
+} uvo_pose_trace_lin;
+typedef struct uvo_pose_trace_trial {
+  int32_t lin;             /* index of its linearisation */
+  int32_t ok;              /* the solve succeeded */
+  int32_t accepted;
+  int32_t pad_;
+  double lambda;           /* as used by this trial */
+  double cur, tmp;         /* currentChi and tempChi (DBL_MAX after a failed solve) */
+  double scale;            /* computeScale() + 1e-3 */
+} uvo_pose_trace_trial;
+typedef struct uvo_pose_trace {
+  int32_t n_lin, n_trials;
+  double R[9], t[3];       /* the final pose in double */
+  uvo_pose_trace_lin lin[32];
+  uvo_pose_trace_trial trial[320];
+} uvo_pose_trace;
+
+/* max_problems 1..64, max_points 1..16384 (UVO_E_BADARG otherwise).  The set launches in the KLT handle's stream and must be
+ * destroyed before it. */
+int uvo_pose_optimizer_create(uvo_klt* k, int max_problems, int max_points, uvo_pose_optimizer** out);
+void uvo_pose_optimizer_destroy(uvo_pose_optimizer* o);
+/* results[j] answers problems[j].  UVO_E_CAPACITY: n_problems > max_problems, an n > max_points, an outlier mask shorter than n.
+ * UVO_E_BADARG: null pointers, negative counts.  Nothing is written on an error.  n_problems == 0 is a no-op. */
+int uvo_pose_optimize(uvo_pose_optimizer* o, const uvo_pose_problem* problems, int n_problems, uvo_pose_result* results);
+/* test tap: the trace of problem `problem` of the set's last call (UVO_E_BADARG when the last call had no such problem). */
+int uvo_pose_optimizer_trace(uvo_pose_optimizer* o, int problem, uvo_pose_trace* out);
+
+/* ------------------------------------------------------------------------------------------------
  * Sim3Solver -- replaces USLAM::Sim3Solver (include/Sim3Solver.h, src/Sim3Solver.cc) as LoopClosing::ComputeSim3 uses it
  * (src/LoopClosing.cc:373-479): one solver per loop candidate, SetRansacParameters(0.99,2,300), then iterate(5,...) over the candidates
  * in turn until one returns a similarity, whose R, t, s go to SearchBySim3 (uvo_sim3_relative, uvo_search_by_sim3 on the same handle).

@@ -45,6 +45,7 @@ ABI_SYMBOLS = [
     "uvo_search_by_projection_kf", "uvo_search_by_bow", "uvo_search_for_triangulation", "uvo_search_for_triangulation_batch", "uvo_search_for_triangulation_next", "uvo_triangulate_matches", "uvo_create_new_map_points", "uvo_fuse", "uvo_fuse_batch", "uvo_project_points", "uvo_search_points_in_frustum", "uvo_sim3_decompose", "uvo_sim3_relative", "uvo_project_sim3", "uvo_search_by_projection_sim3", "uvo_search_by_sim3", "uvo_haloc_hash", "uvo_klt_create", "uvo_klt_destroy", "uvo_klt_build_pyramid", "uvo_klt_build_pyramid_from_extractor", "uvo_klt_read_level", "uvo_klt_track", "uvo_undistort_points", "uvo_klt_track_undistorted", "uvo_klt_find_fundamental", "uvo_klt_track_filtered", "uvo_klt_fm_hypotheses", "uvo_klt_solve_pnp_ransac", "uvo_klt_pnp_hypotheses", "uvo_vocabulary_create", "uvo_vocabulary_destroy", "uvo_bow_transform", "uvo_matcher_wait_extractor", "uvo_extractor_wait_matcher", "uvo_matcher_attach_extractor", "uvo_matcher_profile",
     "uvo_glibc_srand", "uvo_glibc_rand_next", "uvo_pnpsolver_set_create", "uvo_pnpsolver_set_destroy", "uvo_pnpsolver_set_clear", "uvo_pnpsolver_add",
     "uvo_pnpsolver_query", "uvo_pnpsolver_iterate", "uvo_pnpsolver_hypotheses",
+    "uvo_pose_optimizer_create", "uvo_pose_optimizer_destroy", "uvo_pose_optimize", "uvo_pose_optimizer_trace",
     "uvo_sim3solver_set_create", "uvo_sim3solver_set_destroy", "uvo_sim3solver_set_clear", "uvo_sim3solver_add", "uvo_sim3solver_set_ransac_parameters",
     "uvo_sim3solver_query", "uvo_sim3solver_iterate", "uvo_sim3solver_find", "uvo_sim3solver_hypotheses",
     "uvo_initializer_create", "uvo_initializer_destroy", "uvo_initializer_set_reference", "uvo_initializer_initialize", "uvo_initializer_hypotheses",
@@ -279,6 +280,11 @@ def _load():
     lib.uvo_pnpsolver_query.argtypes = [vp, ci, vp]
     lib.uvo_pnpsolver_iterate.argtypes = [vp, vp, ci, ci, vp, vp]
     lib.uvo_pnpsolver_hypotheses.argtypes = [vp, ci, vp, vp, vp, ci, vp]
+    lib.uvo_pose_optimizer_create.argtypes = [vp, ci, ci, vp]
+    lib.uvo_pose_optimizer_destroy.argtypes = [vp]
+    lib.uvo_pose_optimizer_destroy.restype = None
+    lib.uvo_pose_optimize.argtypes = [vp, vp, ci, vp]
+    lib.uvo_pose_optimizer_trace.argtypes = [vp, ci, vp]
     lib.uvo_sim3solver_set_create.argtypes = [vp, ci, ci, vp]
     lib.uvo_sim3solver_set_destroy.argtypes = [vp]
     lib.uvo_sim3solver_set_destroy.restype = None
@@ -1450,6 +1456,113 @@ class PnPsolverSet:
         if rc:
             raise UvoError(rc, "uvo_pnpsolver_hypotheses")
         return sub[:n.value].copy(), poses[:n.value].copy(), cnt[:n.value].copy()
+
+
+class PoseProblemC(ctypes.Structure):
+    """uvo_pose_problem."""
+    _fields_ = [("p3d", ctypes.c_void_p), ("p2d", ctypes.c_void_p), ("inv_sigma2", ctypes.c_void_p), ("n", ctypes.c_int32), ("fx", ctypes.c_float),
+                ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float), ("Tcw", ctypes.c_float * 16), ("pad_", ctypes.c_int32)]
+
+
+class PoseResultC(ctypes.Structure):
+    """uvo_pose_result."""
+    _fields_ = [("Tcw", ctypes.c_float * 16), ("n_inliers", ctypes.c_int32), ("rounds", ctypes.c_int32), ("outlier", ctypes.c_void_p),
+                ("outlier_cap", ctypes.c_int32), ("pad_", ctypes.c_int32)]
+
+
+class PoseTraceLin(ctypes.Structure):
+    """uvo_pose_trace_lin."""
+    _fields_ = [("round", ctypes.c_int32), ("iteration", ctypes.c_int32), ("H", ctypes.c_double * 21), ("b", ctypes.c_double * 6), ("chi2", ctypes.c_double)]
+
+
+class PoseTraceTrial(ctypes.Structure):
+    """uvo_pose_trace_trial."""
+    _fields_ = [("lin", ctypes.c_int32), ("ok", ctypes.c_int32), ("accepted", ctypes.c_int32), ("pad_", ctypes.c_int32), ("lambda_", ctypes.c_double),
+                ("cur", ctypes.c_double), ("tmp", ctypes.c_double), ("scale", ctypes.c_double)]
+
+
+class PoseTraceC(ctypes.Structure):
+    """uvo_pose_trace."""
+    _fields_ = [("n_lin", ctypes.c_int32), ("n_trials", ctypes.c_int32), ("R", ctypes.c_double * 9), ("t", ctypes.c_double * 3),
+                ("lin", PoseTraceLin * 32), ("trial", PoseTraceTrial * 320)]
+
+
+POSE_LIN_DTYPE = np.dtype([("round", "<i4"), ("iteration", "<i4"), ("H", "<f8", 21), ("b", "<f8", 6), ("chi2", "<f8")])
+POSE_TRIAL_DTYPE = np.dtype([("lin", "<i4"), ("ok", "<i4"), ("accepted", "<i4"), ("pad_", "<i4"), ("lambda", "<f8"), ("cur", "<f8"), ("tmp", "<f8"),
+                             ("scale", "<f8")])
+
+
+class PoseTrace:
+    """The test tap of one problem: R float64[3, 3], t float64[3], lin (POSE_LIN_DTYPE, one record per linearisation), trial
+    (POSE_TRIAL_DTYPE, one per Levenberg trial)."""
+
+    def __init__(self, c):
+        self.R, self.t = np.array(c.R, np.float64).reshape(3, 3), np.array(c.t, np.float64)
+        self.lin = np.frombuffer(bytes(c.lin), POSE_LIN_DTYPE)[:c.n_lin].copy()
+        self.trial = np.frombuffer(bytes(c.trial), POSE_TRIAL_DTYPE)[:c.n_trials].copy()
+
+
+class PoseResult:
+    """One optimised problem: Tcw float32[4, 4], n_inliers (the reference's return value), rounds, outlier uint8[n]."""
+
+    def __init__(self, c, outlier):
+        self.Tcw = np.array(c.Tcw, np.float32).reshape(4, 4)
+        self.n_inliers, self.rounds, self.outlier = c.n_inliers, c.rounds, outlier
+
+
+class PoseOptimizer:
+    """Optimizer::PoseOptimization(Frame*) (src/Optimizer.cc:2012-2145) on a KLT handle: optimize() takes a list of independent problems
+    and runs them as one device call.  `_api` exists so that the tests can drive another build through this class."""
+
+    def __init__(self, klt, max_problems=1, max_points=4096, _api=None):
+        self._api = _api if _api is not None else lib
+        self._klt = klt   # the set launches in the handle's stream: keep it alive
+        self._h = ctypes.c_void_p()
+        self.max_problems, self.max_points = max_problems, max_points
+        rc = self._api.uvo_pose_optimizer_create(klt._h if klt is not None else None, max_problems, max_points, ctypes.byref(self._h))
+        if rc:
+            self._h = None
+            raise UvoError(rc, "uvo_pose_optimizer_create")
+
+    def close(self):
+        if getattr(self, "_h", None) and self._api is not None:
+            self._api.uvo_pose_optimizer_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def optimize(self, problems, outlier_cap=None):
+        """problems: a list of (p3d [n, 3], p2d [n, 2], inv_sigma2 [n], K = (fx, fy, cx, cy), Tcw [4, 4]) -> a list of PoseResult.
+        outlier_cap (for the tests): the mask capacity passed for every problem instead of its n."""
+        cp = (PoseProblemC * max(len(problems), 1))()
+        cr = (PoseResultC * max(len(problems), 1))()
+        keep, masks = [], []
+        for j, (p3d, p2d, w, K, Tcw) in enumerate(problems):
+            a = np.ascontiguousarray(p3d, np.float32).reshape(-1, 3)
+            b = np.ascontiguousarray(p2d, np.float32).reshape(-1, 2)
+            c = np.ascontiguousarray(w, np.float32).reshape(-1)
+            if not (len(a) == len(b) == len(c)):
+                raise ValueError("p3d, p2d and inv_sigma2 differ in length")
+            T = np.ascontiguousarray(Tcw, np.float32).reshape(16)
+            m = np.zeros(max(len(a), 1), np.uint8)
+            keep.append((a, b, c))
+            masks.append(m)
+            cp[j].p3d, cp[j].p2d, cp[j].inv_sigma2, cp[j].n = a.ctypes.data, b.ctypes.data, c.ctypes.data, len(a)
+            cp[j].fx, cp[j].fy, cp[j].cx, cp[j].cy = [float(v) for v in K]
+            cp[j].Tcw = (ctypes.c_float * 16)(*T.tolist())
+            cr[j].outlier, cr[j].outlier_cap = m.ctypes.data, len(a) if outlier_cap is None else outlier_cap
+        rc = self._api.uvo_pose_optimize(self._h, cp, len(problems), cr)
+        if rc:
+            raise UvoError(rc, "uvo_pose_optimize")
+        return [PoseResult(cr[j], masks[j][:cp[j].n].copy()) for j in range(len(problems))]
+
+    def trace(self, problem=0):
+        """Test tap: PoseTrace of problem `problem` of the last optimize() call."""
+        c = PoseTraceC()
+        rc = self._api.uvo_pose_optimizer_trace(self._h, problem, ctypes.byref(c))
+        if rc:
+            raise UvoError(rc, "uvo_pose_optimizer_trace")
+        return PoseTrace(c)
 
 
 class Sim3SolverParams(ctypes.Structure):
