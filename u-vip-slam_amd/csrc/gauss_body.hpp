@@ -44,6 +44,10 @@ struct GaussPlans {
 int gauss7_rows_per_seg(int batch);
 int gauss7_blocks_per_frame(const Geom& g, int rows_per_seg);
 GaussPlans gauss7_plans(const Geom& g, int rows_per_seg);
+#ifndef UVO_GAUSS_PK_COLUMN
+#define UVO_GAUSS_PK_COLUMN 0  // 1: the column pass's multiply-adds on pixel pairs (measured and dropped again: DESIGN.md section 7.3)
+#endif
+typedef float f32x2 __attribute__((ext_vector_type(2)));
 constexpr int GS_TILES = 16;  // tiles a wavefront collects per 8-row group: 15 of a full strip, 2 x 7 / 4 x 3 of the narrow ones
 // SSE2: the rounding contract of an x86-64 OpenCV build (UVO_TUNE_BLUR_ROUNDING, the default): SymmColumnVec_32s8u's vector body -- image
 // columns 0 .. (w & ~3) - 1 -- converts the exact fp32 column sum with cvtps2dq + two saturating packs, i.e. round to nearest, an exact .5 to
@@ -65,28 +69,38 @@ __device__ __forceinline__ void gauss7_body(int block, int blocks_x, int batch, 
   const int vbx = vb % blocks_x, f = vb / blocks_x;  // an XCD walks whole frames, item after item
   int item = vbx * 4 + wave_in_block();
   const int lane = threadIdx.x & 63;
+  // Everything from here to the lane's own column is wave-uniform and has to stay in scalar registers: the row loop's counter, its exit,
+  // the row addresses and the flush's row tests are derived from it.  The level search has the form of fast_region (fast_geom.hpp) and
+  // takes the plan by reference: the compiler then reads the by-value kernel argument where it lies, with scalar loads.  (With a search
+  // that returned from inside the loop and a copy of the plan, k_gauss7 copied the whole argument to scratch and read it back with vector
+  // loads: the item, the level, the plan, py0, nsrc, the phase ... were vector values and the row loop a divergent one --
+  // tests/test_kernel_resources_blur_walk.py holds the loop's control to the scalar unit.)
   int level = 0;
-  for (;; ++level) {
-    if (item < plans.p[level].items) break;
-    item -= plans.p[level].items;
-    if (level == nlevels - 1) return;
+  for (; level < nlevels; ++level) {
+    const int n = plans.p[level].items;
+    if (item < n) break;
+    item -= n;
   }
-  const StripPlan plan = plans.p[level];
-  const LevelGeom g = lv[level];
+  if (level == nlevels) return;
+  const StripPlan& plan = plans.p[level];
+  const LevelGeom g = lv[level];  // (scalar loads of the fields used)
   int strip_x, seg, nsub;
   fast_strip_item(plan, item, strip_x, seg, nsub);
-  // The walk, in two instantiations: over a padded plane, or (IP) over level 0 read in place -- the caller's image, whose 16-pixel
+  // The walk, instantiated over a padded plane or (IP) over level 0 read in place -- the caller's image, whose 16-pixel
   // REFLECT_101 border (the blur reaches 3 pixels of it, and copies 4 into the blurred plane's ring) is produced by reflecting the row
   // index and, per lane, the column run: a lane's four pixels are an aligned group of four image columns (the width is a multiple of 4 in
   // this mode), so a group is wholly inside the image or wholly a reversed run of it -- one load and one byte permute either way.
-  auto walk = [&](auto ip_tag, auto tail_tag) {
+  // FULL: an ordinary strip (nsub == 1) -- the lane's rows are the wavefront's, so the row index, the image-row test and the range of
+  // the direct stores need no per-lane arithmetic at all; the narrow strips keep a per-lane row offset (sub * rows_per_seg).
+  auto walk = [&](auto ip_tag, auto tail_tag, auto full_tag) {
   constexpr bool IP = decltype(ip_tag)::value;
   constexpr bool TAIL = decltype(tail_tag)::value;  // SSE2 contract: the wavefront holds output columns of the scalar tail (decided once, below: no test in the row loop)
+  constexpr bool FULL = decltype(full_tag)::value;
   const uint8_t* src = IP ? l0.vbase + f * l0.frame_stride + (int64_t)kPad * l0.pitch + kPad : pyr + f * pyr_block + g.plane_off;  // IP: the image's origin
   const int spitch = IP ? l0.pitch : g.pitch;
   uint8_t* dst = blur + f * pyr_block + g.plane_off;
 
-  const int lps = 64 / nsub, sub = (lane * nsub) >> 6, ls = lane - sub * lps;
+  const int lps = FULL ? 64 : 64 / nsub, sub = FULL ? 0 : (lane * nsub) >> 6, ls = lane - sub * lps;
   // padded-plane column of this lane's dword; the first lane of a sub-strip is its left halo.  Region = padded cols [12, w+20).
   const int X = 8 + strip_x + ls * 4;
   int Xc = X > g.pitch - 4 ? g.pitch - 4 : X;  // clamp loads into the row (only halo / out-of-region lanes)
@@ -100,17 +114,18 @@ __device__ __forceinline__ void gauss7_body(int block, int blocks_x, int batch, 
   }
   // padded-plane rows: region rows [12, h+20); the lane's segment rows [py0l, py1l)
   const int py0 = 12 + seg * rows_per_seg;
-  const int py0l = py0 + sub * rows_per_seg;
+  const int sub_rows = sub * rows_per_seg;  // the lane's sub-strip lies this many rows below sub-strip 0
+  const int py0l = py0 + sub_rows;
   const int py1l = min(py0l + rows_per_seg, g.h + 20);
   const bool lane_out = ls >= 1 && ls <= lps - 2 && X >= 12 && X < g.w + 20 && py1l > py0l;
-  const int tile_col = (X >> 4) * 128 + (X & 15);   // the lane's place inside a row of tiles
-  const int64_t tile_row_bytes = (int64_t)g.pitch * 8;  // (pitch / 16) tiles of 128 bytes
+  const uint32_t tile_col = (uint32_t)((X >> 4) * 128 + (X & 15));  // the lane's place inside a row of tiles
+  const uint32_t tile_row_bytes = (uint32_t)g.pitch * 8u;           // (pitch / 16) tiles of 128 bytes
   // Output goes to the plane in whole cache lines: the tiles a sub-strip's output lanes cover completely (columns
   // [16 t_first, 16 (t_last + 1)) of its output range) are collected in LDS -- eight rows of the walk fill them -- and written out as
   // 16 bytes per lane, eight lanes per 128-byte line; the few columns left and right of them are stored directly, a dword per row.
   const int x_lo = max(12, 8 + strip_x + 4), x_hi = min(g.w + 20, 8 + strip_x + 4 * (lps - 1));  // output columns of the sub-strip
   const int t_first = (x_lo + 15) >> 4, nts = max((x_hi >> 4) - t_first, 0);                    // its full tiles: t_first .. t_first + nts - 1
-  const int ts_shift = nsub == 1 ? 4 : (nsub == 2 ? 3 : 2), TS = 1 << ts_shift;                 // LDS tile slots per sub-strip (16 / nsub >= nts)
+  const int ts_shift = (FULL || nsub == 1) ? 4 : (nsub == 2 ? 3 : 2), TS = 1 << ts_shift;       // LDS tile slots per sub-strip (16 / nsub >= nts)
   const bool via_lds = lane_out && (X >> 4) >= t_first && (X >> 4) < t_first + nts;
   uint32_t* stile = s_tile[wave_in_block()];
   // + (py & 7) * 4: dword of the lane's pixels in the tile.  Lanes that collect nothing write their own dword behind the tiles -- the
@@ -119,27 +134,27 @@ __device__ __forceinline__ void gauss7_body(int block, int blocks_x, int batch, 
   // The write-out of a group: task t = lane + 64 it (it = 0, 1) is row t & 7 of tile slot t >> 3; everything about a task that does not
   // depend on the group is worked out here, once.
   // (row addresses: a sub-strip's rows lie s * rows_per_seg below sub-strip 0's, a whole number of tile rows, so every address is
-  // "tile row of sub-strip 0" -- wave-uniform, scalar arithmetic -- plus a per-lane constant)
-  const int64_t seg_tile_rows = (int64_t)(rows_per_seg >> 3) * tile_row_bytes;
-  const int64_t lane_goff = (int64_t)sub * seg_tile_rows + tile_col;  // the lane's own dword relative to sub-strip 0's tile row
-  int f_lds[2], f_p0[2], f_p1[2], f_rowoff[2];
-  int64_t f_goff[2];
+  // "tile row of sub-strip 0" -- wave-uniform: a scalar base -- plus a per-lane 32-bit constant: a plane is far below 4 GB)
+  const uint32_t seg_tile_rows = (uint32_t)(rows_per_seg >> 3) * tile_row_bytes;
+  const uint32_t lane_goff = (uint32_t)sub * seg_tile_rows + tile_col;  // the lane's own dword relative to sub-strip 0's tile row
+  // a task's rows in the plane are [p0, p1) of its own sub-strip, i.e. the groups whose row pyg (of sub-strip 0) lies in [f_lo, f_hi)
+  int f_lds[2], f_lo[2], f_hi[2];
+  uint32_t f_goff[2];
 #pragma unroll
   for (int it = 0; it < 2; ++it) {
     const int t = lane + 64 * it, row = t & 7, slot = t >> 3, s_ = slot >> ts_shift, ti = slot & (TS - 1);
     const int p0 = py0 + s_ * rows_per_seg;
+    const int p1 = (s_ < nsub && ti < nts) ? min(p0 + rows_per_seg, g.h + 20) : p0;  // empty range: no such tile
     f_lds[it] = (slot << 5) + (row << 2);
-    f_goff[it] = (int64_t)s_ * seg_tile_rows + (t_first + ti) * 128 + (row << 4);
-    f_rowoff[it] = s_ * rows_per_seg + row;
-    f_p0[it] = p0, f_p1[it] = (s_ < nsub && ti < nts) ? min(p0 + rows_per_seg, g.h + 20) : p0;  // empty range: no such tile
+    f_goff[it] = (uint32_t)s_ * seg_tile_rows + (uint32_t)((t_first + ti) * 128 + (row << 4));
+    f_lo[it] = p0 - (s_ * rows_per_seg + row), f_hi[it] = p1 - (s_ * rows_per_seg + row);
   }
   // writes rows 0 .. r_hi of the 8-row group that starts at padded row pyg (of sub-strip 0) of every collected tile to the plane
-  auto flush_tiles = [&](int pyg, int r_hi, int64_t group_base) {  // group_base = byte offset of the group's tile row (sub-strip 0)
+  auto flush_tiles = [&](int pyg, int r_hi, uint32_t group_base) {  // group_base = byte offset of the group's tile row (sub-strip 0)
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
     for (int it = 0; it < 2; ++it) {
-      const int prow = pyg + f_rowoff[it];  // the row of the task's own sub-strip in the plane
-      if ((lane & 7) <= r_hi && prow >= f_p0[it] && prow < f_p1[it]) {
+      if ((lane & 7) <= r_hi && pyg >= f_lo[it] && pyg < f_hi[it]) {
         const uint4 v = *reinterpret_cast<const uint4*>(stile + f_lds[it]);
         *reinterpret_cast<uint4*>(dst + (group_base + f_goff[it])) = v;
       }
@@ -152,10 +167,13 @@ __device__ __forceinline__ void gauss7_body(int block, int blocks_x, int batch, 
 #pragma unroll
   for (int k = 0; k < 4; ++k) inmask |= (X + k >= kPad && X + k < g.w + kPad) ? 0xffu << (8 * k) : 0u;
   const int nsrc = min(py0 + rows_per_seg, g.h + 20) - py0 + 6;  // source rows py0-3 .. py1+2 of sub-strip 0 (the longest)
-  // per lane, in loop rows: output row py = py0l + j - 6 lies inside the image rows for j in [j_in0, j_in0 + n_in), and the lane stores
-  // it directly (an output lane outside the collected tiles) for j < j_edge1
-  const uint32_t j_in0 = (uint32_t)(kPad - py0l + 6), n_in = (uint32_t)g.h;
-  const uint32_t j_edge1 = (lane_out && !via_lds) ? (uint32_t)max(py1l - py0l + 6, 0) : 0u;
+  // in loop rows: output row py = py0l + j - 6 lies inside the image rows for j in [j_in0, j_in0 + n_in) -- of the wavefront (FULL) or
+  // per lane -- and a lane stores it directly (an output lane outside the collected tiles) for j < j_edge1: FULL, that is every row of
+  // the loop, and the test is the lane's own constant
+  const uint32_t j_in0s = (uint32_t)(kPad - py0 + 6), n_in = (uint32_t)g.h;
+  const uint32_t j_in0 = j_in0s - (uint32_t)sub_rows;
+  const bool direct_lane = lane_out && !via_lds;
+  const uint32_t j_edge1 = direct_lane ? (uint32_t)max(py1l - py0l + 6, 0) : 0u;
 
   const GaussRowTaps RT = gauss_row_taps(taps);
   // column taps scaled by 2^-16 (exact): the column sum comes out as sum / 65536 -- every partial sum an exact multiple of 2^-16 below 2^8
@@ -168,31 +186,52 @@ __device__ __forceinline__ void gauss7_body(int block, int blocks_x, int batch, 
   uint32_t cring[7];
   // Row loads are issued one unrolled block (7 rows) ahead of their use: a wavefront walks ~70 rows one after another, so
   // without the prefetch every row would expose a full memory round trip.
-  auto load_row = [&](int j) -> uint32_t {
-    int prow = py0l - 3 + j;
+  // A block's seven rows are padded rows p .. p + 6 of sub-strip 0 and the same rows sub_rows lower in the other sub-strips.  Only the
+  // first and the last block of a level can touch a row that has to be reflected (IP) or clamped into the plane, and whether this block
+  // does is a scalar test: every other block takes its rows' offsets from the scalar unit.
+  // Addresses are the plane's wave-uniform pointer plus a 32-bit lane offset (a plane is far below 4 GB; a 64-bit add per lane issues
+  // at a quarter of the rate): the row's scalar offset plus the lane's constant -- its sub-strip's rows and its column -- one add per
+  // row.  FULL: the row is the wavefront's, so reflecting / clamping it in an edge block is scalar work too.
+  const uint32_t lane_src = (uint32_t)sub_rows * (uint32_t)spitch + (uint32_t)Xc;
+  const int sub_rows_max = FULL ? 0 : (nsub - 1) * rows_per_seg;
+  auto edge_row = [&](int p) -> uint32_t {  // the row to load for padded row p (IP: image row p): reflected (IP), clamped into the plane
     if (IP) {
-      int r = prow - kPad;                      // image row; REFLECT_101 above and below
-      r = r < 0 ? -r : r;
+      int r = p < 0 ? -p : p;                   // REFLECT_101 above and below
       r = r > g.h - 1 ? 2 * (g.h - 1) - r : r;
-      r = r < 0 ? 0 : r;                        // (rows past the border's reach are never used by a valid output)
-      const uint32_t v = *reinterpret_cast<const uint32_t*>(src + (__umul24((uint32_t)r, (uint32_t)spitch) + (uint32_t)Xc));  // (see below)
-      return __builtin_amdgcn_perm(v, v, csel);
+      return (uint32_t)(r < 0 ? 0 : r);         // (rows past the border's reach are never used by a valid output)
     }
-    prow = prow > g.ph - 1 ? g.ph - 1 : prow;  // rows past the plane are never used by a valid output
-    // wave-uniform base + 32-bit lane offset by a 24-bit multiply (a plane is far below 4 GB; a 64-bit multiply-add issues at a quarter of the rate)
-    return *reinterpret_cast<const uint32_t*>(src + (__umul24((uint32_t)prow, (uint32_t)spitch) + (uint32_t)Xc));
+    return (uint32_t)(p > g.ph - 1 ? g.ph - 1 : p);  // rows past the plane are never used by a valid output
+  };
+  auto load_block = [&](int j0, uint32_t* rows) {  // rows[u] = loop row j0 + u; unconditional (see below)
+    const int p_first = py0 - 3 + j0 - (IP ? kPad : 0), p_last = p_first + 6 + sub_rows_max;  // IP: image rows
+    const bool inside = p_first >= 0 && p_last <= (IP ? g.h : g.ph) - 1;
+    uint32_t off[7];
+    if (inside) {
+      const uint32_t o = (uint32_t)p_first * (uint32_t)spitch;
+#pragma unroll
+      for (int u = 0; u < 7; ++u) off[u] = (o + (uint32_t)(u * spitch)) + lane_src;
+    } else if (FULL) {
+#pragma unroll
+      for (int u = 0; u < 7; ++u) off[u] = edge_row(p_first + u) * (uint32_t)spitch + (uint32_t)Xc;
+    } else {
+#pragma unroll
+      for (int u = 0; u < 7; ++u) off[u] = __umul24(edge_row(p_first + u + sub_rows), (uint32_t)spitch) + (uint32_t)Xc;
+    }
+#pragma unroll
+    for (int u = 0; u < 7; ++u) {
+      const uint32_t v = *reinterpret_cast<const uint32_t*>(src + off[u]);
+      rows[u] = IP ? __builtin_amdgcn_perm(v, v, csel) : v;
+    }
   };
   // byte offset of sub-strip 0's current output row inside its tile column: tile row * tile_row_bytes + (row % 8) * 16, advanced row by
-  // row (one scalar add instead of a 64-bit multiply per row)
-  int64_t rowb = (int64_t)(py0 >> 3) * tile_row_bytes + ((py0 & 7) << 4);
+  // row (one scalar add instead of a multiply per row)
+  uint32_t rowb = (uint32_t)(py0 >> 3) * tile_row_bytes + (uint32_t)((py0 & 7) << 4);
   int phase = (py0 - 6) & 7;  // (row of sub-strip 0) & 7 of loop row j = 0, advanced with it
   uint32_t cur[7], nxt[7];
-#pragma unroll
-  for (int u = 0; u < 7; ++u) cur[u] = load_row(u);  // unconditional (the row index is clamped into the plane): with a branch around a load
-                                                     // the compiler cannot count the loads in flight and waits for all of them
+  load_block(0, cur);  // unconditional (the row index is clamped into the plane): with a branch around a load that the other side does
+                       // not issue the compiler cannot count the loads in flight and waits for all of them
   for (int base = 0; base < nsrc; base += 7) {
-#pragma unroll
-    for (int u = 0; u < 7; ++u) nxt[u] = load_row(base + 7 + u);
+    load_block(base + 7, nxt);
 #pragma unroll
     for (int u = 0; u < 7; ++u) {
       const int j = base + u;
@@ -214,18 +253,34 @@ __device__ __forceinline__ void gauss7_body(int block, int blocks_x, int batch, 
           const float* r5 = hring[(u + 6) % 7];
           const float* r6 = hring[u];
           const uint32_t centre = cring[(u + 4) % 7];
-          const bool row_in = (uint32_t)j - j_in0 < n_in;
+          const bool row_in = (uint32_t)j - (FULL ? j_in0s : j_in0) < n_in;  // FULL: a scalar compare
           // column pass in fp32, one pixel per instruction (v_add_f32 / v_fma_f32); clamp to 255 and the byte insert are the conversion
           // itself.  (Round 5's packed form -- v_pk_add_f32 / v_pk_fma_f32 on pixel pairs -- issues fewer instructions and wins the
           // micro-benchmark, tools/ubench/pk_f32_rate.hip, but needs more registers: 0.238 - 0.246 against 0.229 - 0.231 ms per 257-frame
           // launch at the same occupancy, profiles/r06_blur_occupancy_ab.txt.)
           uint32_t blurred = 0;
+#if UVO_GAUSS_PK_COLUMN
+#pragma unroll
+          for (int kp = 0; kp < 4; kp += 2) {  // the same sums on pixel pairs (v_pk_fma_f32): every operation is exact, so the bytes are the same
+            auto pr = [&](const float* r) { return f32x2{r[kp], r[kp + 1]}; };
+            const f32x2 bias = SSE2 ? f32x2{0.0f, 0.0f} : f32x2{0.5f, 0.5f};
+            const f32x2 z2 = __builtin_elementwise_fma(f32x2{c0, c0}, pr(r0) + pr(r6), __builtin_elementwise_fma(f32x2{c1, c1}, pr(r1) + pr(r5),
+                                 __builtin_elementwise_fma(f32x2{c2, c2}, pr(r2) + pr(r4), __builtin_elementwise_fma(f32x2{c3, c3}, pr(r3), bias))));
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+              float z = z2[e];
+              if (SSE2 && TAIL) z = tail_lane ? __builtin_floorf(z + 0.5f) : z;
+              blurred = __builtin_amdgcn_cvt_pk_u8_f32(z, (uint32_t)(kp + e), blurred);
+            }
+          }
+#else
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
             float z = __builtin_fmaf(c0, r0[k] + r6[k], __builtin_fmaf(c1, r1[k] + r5[k], __builtin_fmaf(c2, r2[k] + r4[k], __builtin_fmaf(c3, r3[k], SSE2 ? 0.0f : 0.5f))));
             if (SSE2 && TAIL) z = tail_lane ? __builtin_floorf(z + 0.5f) : z;  // the scalar tail's columns: floor(sum + .5) is a whole number, which the conversion leaves alone
             blurred = __builtin_amdgcn_cvt_pk_u8_f32(z, (uint32_t)k, blurred);
           }
+#endif
           // pad ring and anything outside the image: the un-blurred centre pixel (byte mask per lane, rows uniform)
           const uint32_t m = row_in ? inmask : 0u;
           const uint32_t out = (blurred & m) | (centre & ~m);
@@ -234,7 +289,7 @@ __device__ __forceinline__ void gauss7_body(int block, int blocks_x, int batch, 
           // eight consecutive rows of the walk complete the line in L2.
           // (py & 7 is the same for every sub-strip: their first rows differ by multiples of rows_per_seg, a multiple of 8)
           stile[lds_slot + (phase_now << 2)] = out;
-          if ((uint32_t)j < j_edge1) *reinterpret_cast<uint32_t*>(dst + rowb + lane_goff) = out;
+          if (FULL ? direct_lane : (uint32_t)j < j_edge1) *reinterpret_cast<uint32_t*>(dst + (rowb + lane_goff)) = out;
           if (phase_now == 7) {
             flush_tiles(py0 + j - 6 - 7, 7, rowb - 112);
             rowb += tile_row_bytes - 112;
@@ -249,19 +304,24 @@ __device__ __forceinline__ void gauss7_body(int block, int blocks_x, int batch, 
   }
   {  // the rows of the last, incomplete group
     const int py_last = py0 + nsrc - 7;  // last output row of sub-strip 0
-    if ((py_last & 7) != 7) flush_tiles(py_last & ~7, py_last & 7, (int64_t)(py_last >> 3) * tile_row_bytes);
+    if ((py_last & 7) != 7) flush_tiles(py_last & ~7, py_last & 7, (uint32_t)(py_last >> 3) * tile_row_bytes);
   }
   };  // walk
   // SSE2: does this wavefront hold output columns of the scalar tail at all?  Only the last strip of a level whose width is no multiple of 4
-  // (and never level 0 in place, whose width is one): those wavefronts take the instantiation with the fix-up in its column pass.
+  // (and never level 0 in place, whose width is one): those wavefronts take the instantiation with the fix-up in its column pass (few
+  // wavefronts: one instantiation, the narrow strips' -- a full strip is a narrow one with one sub-strip).
   const int x_last = 8 + strip_x + 4 * (64 / nsub - 1);  // first padded column behind the strip's lanes
   const bool tail_wave = SSE2 && (g.w & 3) != 0 && kPad + (g.w & ~3) >= 8 + strip_x && kPad + (g.w & ~3) < x_last;
-  if (level == 0 && l0.vbase != nullptr)
-    walk(std::true_type{}, std::false_type{});
-  else if (tail_wave)
-    walk(std::false_type{}, std::true_type{});
-  else
-    walk(std::false_type{}, std::false_type{});
+  const bool in_place = level == 0 && l0.vbase != nullptr;
+  if (tail_wave && !in_place)
+    walk(std::false_type{}, std::true_type{}, std::false_type{});
+  else if (nsub == 1) {
+    if (in_place) walk(std::true_type{}, std::false_type{}, std::true_type{});
+    else walk(std::false_type{}, std::false_type{}, std::true_type{});
+  } else {
+    if (in_place) walk(std::true_type{}, std::false_type{}, std::false_type{});
+    else walk(std::false_type{}, std::false_type{}, std::false_type{});
+  }
 }
 
 
