@@ -75,6 +75,16 @@ typedef struct uvo_extractor_cfg {
  *   - the number of quad-tree roots of a level, round(window width / window height) (:1010), must be 1 .. 64 (`nIni = 0`, an image
  *     more than twice as high as wide, divides by zero in the reference too);
  *   - at most 2^24 FAST cells per frame; nlevels <= 16.
+ * Sizes below max_width x max_height.  A handle takes any image whose sides are both within its maximum and that is inside the
+ * envelope above by itself -- not every such size is: the rules hold for EVERY level of the image's own pyramid.  The smallest square is
+ * the first side whose last level, round(side * invScaleFactor^(nlevels - 1)), still measures 56 px (96 at 1.2 / 4 levels, 99 at
+ * 1.33 / 3; one pixel less is UVO_E_UNSUPPORTED), and the root rule applies to each level's detection window (the level minus 26 px):
+ * 150 x 256 is taken at 1.2 / 4 levels (last window 61 x 122, one root) and refused at 1.33 / 3 (59 x 119 rounds to no root) although
+ * the image is not twice as high as wide.  The host-buffer forms check both sides (UVO_E_BADARG beyond either);
+ * uvo_extract_batch_device checks no side, only the capacities the handle was sized with: other shapes of at most the maximum's area
+ * are taken only where they fit every one of them and refused with UVO_E_BADARG where they do not (the transposed shape 256 x 320 on
+ * a 320 x 256 handle: its planes, or at three levels its row tables, do not fit).  A refused call of either kind leaves the handle as
+ * it was.
  * uvo_sharder additionally needs uvo_extractor_max_keypoints() <= 65535 when it matches (train indices are packed in 16 bits).
  */
 int uvo_extractor_create(const uvo_extractor_cfg* cfg, uvo_extractor** out);

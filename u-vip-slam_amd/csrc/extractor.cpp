@@ -55,16 +55,18 @@ static int set_lane_fast_mode(uvo_extractor* h, int li) {
   return UVO_OK;
 }
 
-static void free_tile_groups(uvo_extractor* h) {
-  for (auto& G : h->tile_groups) h->mem.release(G.d_plan);
-  h->tile_groups.clear();
+static void free_tile_groups(uvo_extractor* h, std::vector<TileGroup>& groups) {
+  for (auto& G : groups) h->mem.release(G.d_plan);
+  groups.clear();
 }
 
-// Compiles the plans of one set of level groups (a tile spec: {first level, tx, ty, threads} each, ascending) for geometry g into
-// h->tile_groups.  A set that cannot be built (a level outside the 12-byte tap window, a tile larger than the LDS) stays empty: the batch
-// then takes the per-level launches.  Called with every lane idle.
-static int build_tile_groups(uvo_extractor* h, const Geom& g) {
-  free_tile_groups(h);
+// Compiles the plans of one set of level groups (a tile spec: {first level, tx, ty, threads} each, ascending) for geometry g, whose resize
+// tables are ctab / rtab / resize_fast, into `out` (plans uploaded; h->tile_groups is not touched).  A set that cannot be built (a level
+// outside the 12-byte tap window, a tile larger than the LDS) stays empty: the batch then takes the per-level launches.  An error leaves
+// `out` empty and nothing allocated.
+static int compile_tile_groups(uvo_extractor* h, const Geom& g, const int* resize_fast, const std::vector<ResizeCol>& ctab, const std::vector<ResizeRow>& rtab,
+                               std::vector<TileGroup>& out) {
+  out.clear();
   const std::vector<uint32_t> spec = h->tile_spec.empty() ? default_tile_spec(g) : h->tile_spec;
   if (spec.empty() || g.nlevels < 2) return UVO_OK;
   PyrTileDims dims[kMaxLevels];
@@ -73,8 +75,8 @@ static int build_tile_groups(uvo_extractor* h, const Geom& g) {
   for (int l = 0; l < g.nlevels; ++l) {
     dims[l] = PyrTileDims{g.lv[l].w, g.lv[l].h, g.lv[l].pitch};
     if (l > 0) {
-      if (!h->resize_fast[l]) return UVO_OK;
-      cp[l] = h->ctab_host.data() + g.lv[l].xtab_off, rp[l] = h->rtab_host.data() + g.lv[l].ytab_off;
+      if (!resize_fast[l]) return UVO_OK;
+      cp[l] = ctab.data() + g.lv[l].xtab_off, rp[l] = rtab.data() + g.lv[l].ytab_off;
     }
   }
   for (size_t k = 0; k < spec.size(); ++k) {
@@ -82,21 +84,34 @@ static int build_tile_groups(uvo_extractor* h, const Geom& g) {
     if (!tile_group_from_spec(spec, k, g.nlevels, G)) break;
     PyrTilePlan P;
     if (G.first < 1 || G.last < G.first || (k == 0 && G.first != 1) || !pyr_tile_plan_build(dims, g.nlevels, G.first, G.last, cp, rp, 4, G.tx, G.ty, h->pyr_tiles_max_lds, P)) {
-      free_tile_groups(h);
+      free_tile_groups(h, out);
       return UVO_OK;
     }
     G.lds = P.lds_bytes;
     int rc = h->mem.alloc(&G.d_plan, P.lv.size());
-    h->tile_groups.push_back(G);  // (owned from here on: the error path frees the whole set)
+    out.push_back(G);  // (owned from here on: the error path frees the whole set)
     if (rc == UVO_OK && hipMemcpy(G.d_plan, P.lv.data(), P.lv.size() * sizeof(PyrTileLevel), hipMemcpyHostToDevice) != hipSuccess) rc = fail(UVO_E_HIP, "plan upload failed");
     if (rc != UVO_OK) {
-      free_tile_groups(h);
+      free_tile_groups(h, out);
       return rc;
     }
   }
   return UVO_OK;
 }
 
+// The handle's set for its current geometry, compiled again (UVO_TUNE_PYR_TILE_GROUP changed the spec).  Called with every lane idle.
+static int build_tile_groups(uvo_extractor* h) {
+  std::vector<TileGroup> groups;
+  const int rc = compile_tile_groups(h, h->geom, h->resize_fast, h->ctab_host, h->rtab_host, groups);
+  free_tile_groups(h, h->tile_groups);  // (an error leaves the empty set: the per-level launches)
+  h->tile_groups.swap(groups);
+  return rc;
+}
+
+// All or nothing: everything a new resolution needs is computed into locals and held against every capacity first -- a refused call leaves
+// the handle, its host tables (resize_fast among them) and its device tables exactly as they were.  Only then the lanes are drained, the
+// tile plans compiled into buffers of their own and the device tables overwritten; a HIP error in that last part (the old tables may be
+// half overwritten) drops the geometry, so that the next call uploads everything again whatever its size.
 int set_geometry(uvo_extractor* h, int width, int height) {
   if (h->have_geom && h->geom.width == width && h->geom.height == height) return UVO_OK;
   Geom g;
@@ -104,45 +119,39 @@ int set_geometry(uvo_extractor* h, int width, int height) {
   std::vector<int32_t> cell_flag;
   int rc = build_geom(h, width, height, g, cells, &cell_flag);
   if (rc) return rc;
-  if (g.pyr_block > h->cap_pyr_block || g.cand_block > h->cap_cand_block || g.total_cells > h->cap_cells || g.sel_block > h->cap_sel_block ||
-      g.flist_cap > h->cap_flist)
-    return fail(UVO_E_BADARG, "image larger than the handle was sized for");
-  size_t cor = 0, cor_n = 0;
-  corner_scratch_size(g, h->cfg.max_batch, 0, &cor, &cor_n);
-  if (cor > h->cap_cor || cor_n > h->cap_cor_n || (size_t)h->cfg.max_batch * fast_flags_per_frame(g) > h->cap_flags)
-    return fail(UVO_E_BADARG, "image larger than the handle was sized for");
   std::vector<ResizeCol> ctab;
   std::vector<ResizeRow> rtab;
-  build_resize_tables(g, ctab, rtab, h->resize_fast);
-  if ((int)ctab.size() > h->cap_xtab || (int)rtab.size() > h->cap_ytab) return fail(UVO_E_BADARG, "image larger than the handle was sized for");
-  // in-flight work may still read the old tables
+  int resize_fast[kMaxLevels] = {0};
+  build_resize_tables(g, ctab, rtab, resize_fast);
+  if (exceeded_capacity(h, g, ctab.size(), rtab.size()) != GEOM_CAP_NONE) return fail(UVO_E_BADARG, "image larger than the handle was sized for");
+  std::vector<uint16_t> oct_tab((size_t)oct_table_entries(g), 0);
+  octree_fill_path_tables(g, oct_tab.data());
+  // ---- the last check is behind us.  In-flight work may still read the old tables
   {
     int rcs = sync_all_lanes(h);
     if (rcs) return rcs;
   }
-  {
-    const LevelGeom& last = g.lv[g.nlevels - 1];
-    const int n_oct = last.oct_tab_off + ((last.bw + last.bh + 1) & ~1);
-    if (n_oct > h->cap_oct_tab) return fail(UVO_E_BADARG, "image larger than the handle was sized for");
-    std::vector<uint16_t> oct_tab((size_t)n_oct, 0);
-    octree_fill_path_tables(g, oct_tab.data());
-    UVO_HIP_CHECK(hipMemcpy(h->d_oct_tab, oct_tab.data(), oct_tab.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+  std::vector<TileGroup> groups;  // in buffers of their own: a failure here has touched nothing the old geometry reads
+  if ((rc = compile_tile_groups(h, g, resize_fast, ctab, rtab, groups)) != UVO_OK) return rc;
+  hipError_t e = hipMemcpy(h->d_oct_tab, oct_tab.data(), oct_tab.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(h->d_lv, g.lv, sizeof(LevelGeom) * g.nlevels, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(h->d_cells, cells.data(), sizeof(CellDesc) * cells.size(), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(h->d_cell_flag, cell_flag.data(), sizeof(int32_t) * cell_flag.size(), hipMemcpyHostToDevice);
+  if (e == hipSuccess && !ctab.empty()) e = hipMemcpy(h->d_ctab, ctab.data(), ctab.size() * sizeof(ResizeCol), hipMemcpyHostToDevice);
+  if (e == hipSuccess && !rtab.empty()) e = hipMemcpy(h->d_rtab, rtab.data(), rtab.size() * sizeof(ResizeRow), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    free_tile_groups(h, groups);
+    h->have_geom = false;  // the device tables are neither the old geometry's nor the new one's
+    hip_err_set(e, "set_geometry table upload");
+    return UVO_E_HIP;
   }
-  UVO_HIP_CHECK(hipMemcpy(h->d_lv, g.lv, sizeof(LevelGeom) * g.nlevels, hipMemcpyHostToDevice));
-  UVO_HIP_CHECK(hipMemcpy(h->d_cells, cells.data(), sizeof(CellDesc) * cells.size(), hipMemcpyHostToDevice));
-  UVO_HIP_CHECK(hipMemcpy(h->d_cell_flag, cell_flag.data(), sizeof(int32_t) * cell_flag.size(), hipMemcpyHostToDevice));
-  if (!ctab.empty()) {
-    UVO_HIP_CHECK(hipMemcpy(h->d_ctab, ctab.data(), ctab.size() * sizeof(ResizeCol), hipMemcpyHostToDevice));
-    UVO_HIP_CHECK(hipMemcpy(h->d_rtab, rtab.data(), rtab.size() * sizeof(ResizeRow), hipMemcpyHostToDevice));
-  }
+  free_tile_groups(h, h->tile_groups);
+  h->tile_groups.swap(groups);
   h->ctab_host.swap(ctab), h->rtab_host.swap(rtab);
-  {
-    int rct = build_tile_groups(h, g);
-    if (rct) return rct;
-  }
+  std::copy(resize_fast, resize_fast + kMaxLevels, h->resize_fast);
   h->geom = g;
-  h->cells = cells;
-  h->cell_flag = cell_flag;
+  h->cells.swap(cells);
+  h->cell_flag.swap(cell_flag);
   h->have_geom = true;
   return UVO_OK;
 }
@@ -385,15 +394,7 @@ int uvo_extractor_create(const uvo_extractor_cfg* cfg, uvo_extractor** out) {
     delete h;
     return rc;
   }
-  // capacities: computed at the maximum size, padded for the small non-monotonicities of the cell grid
-  h->cap_pyr_block = g.pyr_block;
-  h->cap_cand_block = g.cand_block + g.cand_block / 16 + 4096;
-  h->cap_cells = g.total_cells + g.total_cells / 8 + 64;
-  h->cap_sel_block = g.sel_block;
-  h->cap_flist = g.flist_cap;
-  h->cap_xtab = 0, h->cap_ytab = 0;
-  for (int l = 1; l < g.nlevels; ++l) h->cap_xtab += g.lv[l].pitch + 64, h->cap_ytab += g.lv[l].ph + 8;  // (row tables are padded to groups of 4 rows; smaller images of the same area have other level heights)
-  h->cap_oct_tab = 2 * g.nlevels * (cfg->max_width + cfg->max_height + 2) + 64;  // (a level's window is never wider / higher than the image; x 2: other shapes of the same area)
+  size_capacities(h, g);
   const size_t B = (size_t)cfg->max_batch;
   hipError_t e = hipSetDevice(h->device);
   if (e != hipSuccess) {
@@ -406,11 +407,6 @@ int uvo_extractor_create(const uvo_extractor_cfg* cfg, uvo_extractor** out) {
     uvo_extractor_destroy(h);      \
     return rc;                     \
   }
-  // corner-list regions: sized for every segment height the launcher may pick, at the maximum resolution
-  size_t ce = 0, cn = 0;
-  corner_scratch_size(g, cfg->max_batch, 8, &ce, &cn);
-  h->cap_cor = ce + ce / 8, h->cap_cor_n = cn + cn / 8 + 64;
-  h->cap_flags = (size_t)B * ((size_t)fast_flags_per_frame(g) + fast_flags_per_frame(g) / 8 + 64);
   A(prepare_pyr_tiles(&h->pyr_tiles_max_lds));
   A(alloc_lane(h, 0));
   A(h->mem.alloc(&h->d_lv, (size_t)kMaxLevels));
@@ -573,7 +569,7 @@ int uvo_extractor_tune(uvo_extractor* h, int knob, int value) {
       if (rc) return rc;
       if (value == 0 || first == 1) h->tile_spec.clear();
       if (value != 0) h->tile_spec.push_back((uint32_t)value);
-      return h->have_geom ? build_tile_groups(h, h->geom) : UVO_OK;
+      return h->have_geom ? build_tile_groups(h) : UVO_OK;
     }
     case UVO_TUNE_PYR_RING:
       if (value != 0 && value != 4 && value != 8 && value != 12) return fail(UVO_E_BADARG, "UVO_TUNE_PYR_RING takes 0, 4, 8 or 12");

@@ -151,6 +151,29 @@ void build_resize_tables(const Geom& g, std::vector<ResizeCol>& ctab, std::vecto
   for (int l = 1; l < g.nlevels; ++l) pyr_build_level_tables(g.lv[l - 1].w, g.lv[l - 1].h, g.lv[l].w, g.lv[l].h, g.lv[l].pitch, ctab, rtab, &fast_ok[l]);
 }
 
+// Rows per (strip, segment) work item.  A wavefront lives for the whole item, so long segments leave a long under-filled
+// tail at the end of the launch (96 rows: +20 % kernel time over 24..32), and the NMS tile of a region has to fit its LDS.
+// A single frame has only ~160 items of 24 rows for 1024 SIMDs: short segments spread it over more wavefronts and shorten the launch.  A
+// wavefront streams its rows + 8 in blocks of 7: 6 rows of work are exactly two blocks (8 rows take three: 20 -> 16 us for one frame).
+#ifndef UVO_FAST_ROWS_FEW
+#define UVO_FAST_ROWS_FEW 6
+#endif
+int fast_rows_per_seg(int batch) { return batch <= 2 ? UVO_FAST_ROWS_FEW : FS_ROWS_MAX; }
+int fast_items_per_frame(const Geom& g, int rows_per_seg) {
+  int items = 0;
+  for (int l = 0; l < g.nlevels; ++l) {
+    FastLevel F;
+    fast_strip_plan(g.lv[l].w - 32, g.lv[l].h - 32, rows_per_seg, F);
+    items += F.items;
+  }
+  return items;
+}
+int fast_flags_per_frame(const Geom& g) {
+  int n = 0;
+  for (int l = 0; l < g.nlevels; ++l) n += g.lv[l].nRows * g.lv[l].nCols;
+  return n;
+}
+
 void corner_scratch_size(const Geom& g, int max_batch, int slack, size_t* entries, size_t* counts) {
   *entries = *counts = 0;
   for (int b = 1; b <= max_batch; b = b < 16 ? b + 1 : max_batch) {
@@ -159,6 +182,44 @@ void corner_scratch_size(const Geom& g, int max_batch, int slack, size_t* entrie
     *counts = std::max(*counts, (size_t)b * it);
     if (b == max_batch) break;
   }
+}
+
+// The capacities a handle fixes at create time, from the geometry g of max_width x max_height: padded for the small non-monotonicities of
+// the cell grid, and for other shapes of the same area
+void size_capacities(uvo_extractor* h, const Geom& g) {
+  const size_t B = (size_t)h->cfg.max_batch;
+  h->cap_pyr_block = g.pyr_block;
+  h->cap_cand_block = g.cand_block + g.cand_block / 16 + 4096;
+  h->cap_cells = g.total_cells + g.total_cells / 8 + 64;
+  h->cap_sel_block = g.sel_block;
+  h->cap_flist = g.flist_cap;
+  h->cap_xtab = 0, h->cap_ytab = 0;
+  for (int l = 1; l < g.nlevels; ++l) h->cap_xtab += g.lv[l].pitch + 64, h->cap_ytab += g.lv[l].ph + 8;  // (row tables are padded to groups of 4 rows; smaller images of the same area have other level heights)
+  h->cap_oct_tab = 2 * g.nlevels * (h->cfg.max_width + h->cfg.max_height + 2) + 64;  // (a level's window is never wider / higher than the image; x 2: other shapes of the same area)
+  // corner-list regions: sized for every segment height the launcher may pick, at the maximum resolution
+  size_t ce = 0, cn = 0;
+  corner_scratch_size(g, h->cfg.max_batch, 8, &ce, &cn);
+  h->cap_cor = ce + ce / 8, h->cap_cor_n = cn + cn / 8 + 64;
+  h->cap_flags = B * ((size_t)fast_flags_per_frame(g) + fast_flags_per_frame(g) / 8 + 64);
+}
+
+int oct_table_entries(const Geom& g) {
+  const LevelGeom& last = g.lv[g.nlevels - 1];
+  return last.oct_tab_off + ((last.bw + last.bh + 1) & ~1);
+}
+
+// Every capacity check of a new geometry (its resize tables hold n_ctab / n_rtab entries) in one place: the first capacity it exceeds
+int exceeded_capacity(const uvo_extractor* h, const Geom& g, size_t n_ctab, size_t n_rtab) {
+  if (g.pyr_block > h->cap_pyr_block || g.cand_block > h->cap_cand_block || g.total_cells > h->cap_cells || g.sel_block > h->cap_sel_block ||
+      g.flist_cap > h->cap_flist)
+    return GEOM_CAP_BLOCKS;
+  size_t cor = 0, cor_n = 0;
+  corner_scratch_size(g, h->cfg.max_batch, 0, &cor, &cor_n);
+  if (cor > h->cap_cor || cor_n > h->cap_cor_n || (size_t)h->cfg.max_batch * fast_flags_per_frame(g) > h->cap_flags) return GEOM_CAP_FAST;
+  if ((int)n_ctab > h->cap_xtab) return GEOM_CAP_XTAB;
+  if ((int)n_rtab > h->cap_ytab) return GEOM_CAP_YTAB;
+  if (oct_table_entries(g) > h->cap_oct_tab) return GEOM_CAP_OCT_TAB;
+  return GEOM_CAP_NONE;
 }
 
 // circular orientation patch (IC_Angle, src/ORBextractor.cc:125-152): rows v in [-15,15], |u| <= umax[|v|] (749 pixels).

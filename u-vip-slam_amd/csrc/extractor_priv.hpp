@@ -162,6 +162,11 @@ namespace uvo {
 void build_ctor_tables(uvo_extractor* h);
 int build_geom(const uvo_extractor* h, int width, int height, Geom& g, std::vector<CellDesc>& cells, std::vector<int32_t>* cell_flag = nullptr);
 void build_resize_tables(const Geom& g, std::vector<ResizeCol>& ctab, std::vector<ResizeRow>& rtab, int* fast_ok);
+void size_capacities(uvo_extractor* h, const Geom& g);
+// which capacity of the handle a geometry exceeds, in the order set_geometry() holds it against them
+enum { GEOM_CAP_NONE = 0, GEOM_CAP_BLOCKS, GEOM_CAP_FAST, GEOM_CAP_XTAB, GEOM_CAP_YTAB, GEOM_CAP_OCT_TAB };
+int exceeded_capacity(const uvo_extractor* h, const Geom& g, size_t n_ctab, size_t n_rtab);
+int oct_table_entries(const Geom& g);  // 2-byte entries of the quad-tree's path tables of geometry g
 // corner-list scratch of geometry g, for the worst batch size up to max_batch (the segment height depends on the batch: fast_rows_per_seg)
 // with `slack` extra work items per frame: *entries for the regions, *counts for their fill counts
 void corner_scratch_size(const Geom& g, int max_batch, int slack, size_t* entries, size_t* counts);
