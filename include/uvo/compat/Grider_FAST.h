@@ -24,7 +24,12 @@ class Grider_FAST {
  public:
   static int perform_griding(uvo_extractor* scratch, const uint8_t* img, int width, int height, ptrdiff_t stride, std::vector<uvo_keypoint>& pts,
                              int num_features, int grid_x, int grid_y, int threshold, bool nonmaxSuppression) {
-    std::vector<uvo_keypoint> out((size_t)num_features + (size_t)grid_x * grid_y + 64);
+    // what the call can return: the per-ROI quota times the ROIs, of which there can be more than grid cells (a call that
+    // uvo_grider_fast refuses still gets a buffer)
+    size_t cap = 1;
+    if (num_features >= 0 && grid_x > 0 && grid_y > 0 && width / grid_x > 0 && height / grid_y > 0)
+      cap = ((size_t)num_features / ((size_t)grid_x * grid_y) + 1) * (size_t)(width / (width / grid_x)) * (size_t)(height / (height / grid_y));
+    std::vector<uvo_keypoint> out(cap);
     int n = 0;
     const int rc = uvo_grider_fast(scratch, img, width, height, stride, num_features, grid_x, grid_y, threshold, nonmaxSuppression ? 1 : 0,
                                    out.data(), (int)out.size(), &n);

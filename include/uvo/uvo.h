@@ -312,6 +312,10 @@ int uvo_extractor_fast_state(uvo_extractor* h, int32_t* pass_threshold, int32_t*
  * out in the reference, so this is the alternative bucketing mode).  Host buffers; keypoints come out ROI-major, inside
  * a ROI by response descending, then y, then x (the reference's std::sort leaves ties unspecified).  Uses the
  * extractor handle's device scratch; the image must fit max_width x max_height.
+ * A ROI is (width / grid_x) x (height / grid_y) pixels and FAST looks at its 3-pixel-inset interior only: a ROI narrower
+ * or lower than 7 pixels has no interior and yields nothing (UVO_OK with *n_out = 0 when no ROI has one), as cv::FAST does
+ * on such a ROI.  At most (num_features / (grid_x * grid_y) + 1) * (width / size_x) * (height / size_y) keypoints come
+ * out -- there can be more ROIs than grid cells; with a smaller cap the call returns UVO_E_CAPACITY and *n_out holds the count.
  */
 int uvo_grider_fast(uvo_extractor* h, const uint8_t* img, int width, int height, ptrdiff_t stride, int num_features, int grid_x, int grid_y,
                     int threshold, int nonmax_suppression, uvo_keypoint* out_kp, int cap, int* n_out);

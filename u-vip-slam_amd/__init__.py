@@ -620,7 +620,10 @@ class ORBextractor:
         """Grider_FAST::perform_griding (include/Grider_FAST.h:81-137)."""
         image = np.ascontiguousarray(image, dtype=np.uint8)
         h, w = image.shape
-        cap = num_features + grid_x * grid_y + 64
+        # what the call can return: the per-ROI quota times the ROIs, of which there can be more than grid cells (w % grid_x >= w // grid_x)
+        size_x, size_y = w // max(grid_x, 1), h // max(grid_y, 1)
+        rois = (w // size_x) * (h // size_y) if size_x > 0 and size_y > 0 else 0
+        cap = max((max(num_features, 0) // max(grid_x * grid_y, 1) + 1) * rois, 1)   # (a call the library refuses still needs a buffer)
         out = np.zeros(cap, KEYPOINT_DTYPE)
         n = ctypes.c_int()
         rc = lib.uvo_grider_fast(self._h, image.ctypes.data, w, h, image.strides[0], num_features, grid_x, grid_y, threshold,

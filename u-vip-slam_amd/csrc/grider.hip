@@ -72,8 +72,11 @@ __global__ __launch_bounds__(256) void k_grid_select(const uint8_t* __restrict__
     // collect the ROI's corners (after NMS) into its list
     if (tid == 0) s_n = 0;
     __syncthreads();
+    // a ROI narrower or lower than 7 px has no interior (cv::FAST returns nothing on it): count 0, the plane is not read.  Two negative
+    // factors would otherwise give a positive product and indices outside the ROI -- and, for the last ROIs, outside the plane
     const int iw = G.size_x - 6, ih = G.size_y - 6;
-    for (int i = tid; i < iw * ih; i += 256) {
+    const int n_in = (iw <= 0 || ih <= 0) ? 0 : iw * ih;
+    for (int i = tid; i < n_in; i += 256) {
       const int lx = 3 + i % iw, ly = 3 + i / iw;
       const uint8_t* q = score + (int64_t)(y0 + ly) * G.w + x0 + lx;
       if (q[0] == 0) continue;
