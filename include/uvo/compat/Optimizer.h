@@ -5,8 +5,19 @@
 //     - int nmatchesMap = Optimizer::PoseOptimization(&mCurrentFrame);
 //     + int nmatchesMap = USLAM::Optimizer::PoseOptimization(poseopt, &mCurrentFrame);     // poseopt: a USLAM::PoseOptimizer
 //
-// With it none of these functions links g2o or Eigen.  The IMU overloads (:319, :779), OptimizeSim3 and the bundle adjustments stay
-// with the reference's Optimizer.
+// With it none of these functions links g2o or Eigen.
+//
+// Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2) (src/Optimizer.cc:2660-2856) over the C ABI's Sim3 optimizer
+// (uvo_sim3_opt* in uvo/uvo.h), for LoopClosing::ComputeSim3 (src/LoopClosing.cc:463):
+//
+//     - g2o::Sim3 gScm(Converter::toMatrix3d(R), Converter::toVector3d(t), s);
+//     - const int nInliers = Optimizer::OptimizeSim3(mpCurrentKF, pKF, vpMapPointMatches, gScm, 10);
+//     + USLAM::Sim3 gScm(R.ptr<float>(), t.ptr<float>(), s);
+//     + const int nInliers = USLAM::Optimizer::OptimizeSim3(sim3opt, mpCurrentKF, pKF, vpMapPointMatches, gScm, 10);  // a USLAM::Sim3Optimizer
+//
+// and an overload over the list of candidates that issues ONE device call; the caller takes the first candidate in order with
+// nInliers >= 10.  With it the path from loop candidate to accepted loop links nothing of the reference's Optimizer.  The IMU overloads
+// of PoseOptimization (:319, :779), OptimizeEssentialGraph and the bundle adjustments stay with the reference's Optimizer.
 //
 // The frame type needs mvpMapPoints (pointers; null where there is no map point; GetWorldPos() returning something with at<float>(i)
 // or operator[]), mvKeysUn (cv::KeyPoint layout), mvInvLevelSigma2, mvbOutlier (std::vector<bool> or anything indexable and
@@ -15,9 +26,17 @@
 // The reference's effects are kept: mvbOutlier[i] = false for every index with a map point before the optimisation, the flags of the
 // last round scattered back to those indices, indices without a map point untouched, the pose written, the count returned.
 // MapPoint::mGlobalMutex is the caller's to hold around the call, as :2049 holds it around the gathering.
+// OptimizeSim3 needs of the key-frame type GetRotation() and GetTranslation() (3 x 3 and 3 x 1 floats, at<float>(i) or operator[] in
+// row-major order), fx, fy, cx, cy (the members GetCalibrationMatrix() is built from), GetMapPointMatches(), GetKeyPointUn(i)
+// (cv::KeyPoint layout), GetInvSigma2(octave) and GetSigma2(octave); of the map-point type isBad(), GetWorldPos() and
+// GetIndexInKeyFrame(pKF).  The reference's effects are kept: the walk of :2713-2792 (a match is skipped -- and its entry in vpMatches1
+// LEFT AS IT IS -- when pMP1 is null, when either point is bad, or when i2 < 0); e12 weighted with pKF1->GetInvSigma2(octave1) and e21
+// with pKF2->GetSigma2(octave2), the variance, as :2781 has it; vpMatches1[idx] nulled for every pair bad in either check; S12 written
+// only when the second round ran, so on the early return (fewer than 10 pairs left: 0 is returned) it is untouched.
 // Header only, C++11, no OpenCV.
 #ifndef UVO_COMPAT_OPTIMIZER_H_
 #define UVO_COMPAT_OPTIMIZER_H_
+#include <cmath>
 #include <vector>
 
 #include "uvo/uvo.h"
@@ -68,7 +87,217 @@ float* pose_data(Frame& F) {
   return detail::mat_data(F.mTcw, 0);
 }
 
+// g2o::Sim3 as far as ComputeSim3 uses it: quaternion (x y z w, not normalised), translation and scale in double.  Built from the
+// solver's floats as g2o::Sim3(Converter::toMatrix3d(R), Converter::toVector3d(t), s) is; those floats are what the optimiser starts
+// from.  A Sim3 that is not built from floats (an optimised one, or one set by hand) starts from its own values rounded to float.
+class Sim3 {
+ public:
+  struct Matrix3 {
+    double m[9];  // row-major
+    double operator()(int r, int c) const { return m[3 * r + c]; }
+  };
+  struct Vector3 {
+    double v[3];
+    double operator[](int i) const { return v[i]; }
+  };
+  Sim3() : s_(1.) { q_[0] = q_[1] = q_[2] = 0., q_[3] = 1., t_[0] = t_[1] = t_[2] = 0., sync(); }
+  Sim3(const float* R, const float* t, float s) : s_(s) {
+    for (int e = 0; e < 9; ++e) Rf_[e] = R[e];
+    for (int e = 0; e < 3; ++e) tf_[e] = t[e], t_[e] = t[e];
+    sf_ = s;
+    // Eigen's Quaternion(Matrix3) on the widened matrix; the optimiser computes the same from the same floats
+    const double m00 = R[0], m11 = R[4], m22 = R[8];
+    double tr = m00 + m11 + m22;
+    if (tr > 0.) {
+      tr = std::sqrt(tr + 1.);
+      q_[3] = 0.5 * tr, tr = 0.5 / tr;
+      q_[0] = ((double)R[7] - R[5]) * tr, q_[1] = ((double)R[2] - R[6]) * tr, q_[2] = ((double)R[3] - R[1]) * tr;
+    } else {
+      int i = 0;
+      if (m11 > m00) i = 1;
+      if (m22 > (double)R[4 * i]) i = 2;
+      const int j = (i + 1) % 3, k = (j + 1) % 3;
+      tr = std::sqrt((double)R[4 * i] - R[4 * j] - R[4 * k] + 1.);
+      q_[i] = 0.5 * tr, tr = 0.5 / tr;
+      q_[3] = ((double)R[3 * k + j] - R[3 * j + k]) * tr;
+      q_[j] = ((double)R[3 * j + i] + R[3 * i + j]) * tr;
+      q_[k] = ((double)R[3 * k + i] + R[3 * i + k]) * tr;
+    }
+  }
+  Sim3(const double* q_xyzw, const double* t, double s) : s_(s) {
+    for (int e = 0; e < 4; ++e) q_[e] = q_xyzw[e];
+    for (int e = 0; e < 3; ++e) t_[e] = t[e];
+    sync();
+  }
+  // Eigen's toRotationMatrix
+  Matrix3 rotation_matrix() const {
+    Matrix3 R;
+    const double tx = 2. * q_[0], ty = 2. * q_[1], tz = 2. * q_[2];
+    const double twx = tx * q_[3], twy = ty * q_[3], twz = tz * q_[3], txx = tx * q_[0], txy = ty * q_[0], txz = tz * q_[0];
+    const double tyy = ty * q_[1], tyz = tz * q_[1], tzz = tz * q_[2];
+    R.m[0] = 1. - (tyy + tzz), R.m[1] = txy - twz, R.m[2] = txz + twy;
+    R.m[3] = txy + twz, R.m[4] = 1. - (txx + tzz), R.m[5] = tyz - twx;
+    R.m[6] = txz - twy, R.m[7] = tyz + twx, R.m[8] = 1. - (txx + tyy);
+    return R;
+  }
+  Vector3 translation() const {
+    Vector3 t;
+    t.v[0] = t_[0], t.v[1] = t_[1], t.v[2] = t_[2];
+    return t;
+  }
+  double scale() const { return s_; }
+  const double* quaternion() const { return q_; }  // x y z w
+  // what the optimiser starts from
+  const float* start_rotation() const { return Rf_; }
+  const float* start_translation() const { return tf_; }
+  float start_scale() const { return sf_; }
+
+ private:
+  void sync() {
+    const Matrix3 R = rotation_matrix();
+    for (int e = 0; e < 9; ++e) Rf_[e] = (float)R.m[e];
+    for (int e = 0; e < 3; ++e) tf_[e] = (float)t_[e];
+    sf_ = (float)s_;
+  }
+  double q_[4], t_[3], s_;
+  float Rf_[9], tf_[3], sf_;
+};
+
+// the owner of the device set: one on the loop-closing thread's matcher handle, sized for the candidates of one ComputeSim3 and the most
+// matches a key frame can carry
+class Sim3Optimizer {
+ public:
+  // the sizes in the order of uvo_sim3_optimizer_create and of the Python class: problems first, then pairs
+  Sim3Optimizer(uvo_matcher* m, int max_problems, int max_pairs) : o_(0) { uvo_sim3_optimizer_create(m, max_problems, max_pairs, &o_); }
+  ~Sim3Optimizer() { uvo_sim3_optimizer_destroy(o_); }
+  bool ok() const { return o_ != 0; }
+  uvo_sim3_optimizer* handle() { return o_; }
+  // gathering buffers of all problems of a call, kept between calls so that a call allocates nothing once they have grown
+  std::vector<float> x1w, x2w, obs1, obs2, info1, info2;
+  std::vector<int32_t> index;    // vnIndexEdge
+  std::vector<int32_t> offset;   // first pair of each problem, and the total
+  std::vector<uint8_t> removed;
+  std::vector<uvo_sim3_opt_problem> problems;
+  std::vector<uvo_sim3_opt_result> results;
+
+ private:
+  Sim3Optimizer(const Sim3Optimizer&);
+  Sim3Optimizer& operator=(const Sim3Optimizer&);
+  uvo_sim3_optimizer* o_;
+};
+
+namespace detail {
+template <class M>
+auto mat_elem(const M& m, int i, int) -> decltype(m.template at<float>(i)) {
+  return m.template at<float>(i);
+}
+template <class M>
+auto mat_elem(const M& m, int i, long) -> decltype(m[i] + 0.f) {
+  return m[i];
+}
+template <class KF>
+void keyframe_of(KF* pKF, uvo_sim3_keyframe& k) {
+  const auto R = pKF->GetRotation();
+  const auto t = pKF->GetTranslation();
+  for (int e = 0; e < 9; ++e) k.Rcw[e] = mat_elem(R, e, 0);
+  for (int e = 0; e < 3; ++e) k.tcw[e] = mat_elem(t, e, 0);
+  k.fx = pKF->fx, k.fy = pKF->fy, k.cx = pKF->cx, k.cy = pKF->cy;
+}
+// :2713-2792: the pairs of one candidate appended to the buffers
+template <class KF, class MP>
+void gather_sim3(Sim3Optimizer& opt, KF* pKF1, KF* pKF2, const std::vector<MP*>& vpMatches1) {
+  const int N = (int)vpMatches1.size();
+  const std::vector<MP*> vpMapPoints1 = pKF1->GetMapPointMatches();
+  for (int i = 0; i < N; i++) {
+    if (!vpMatches1[i]) continue;
+    MP* pMP1 = vpMapPoints1[i];
+    MP* pMP2 = vpMatches1[i];
+    const int i2 = pMP2->GetIndexInKeyFrame(pKF2);
+    if (!(pMP1 && pMP2)) continue;
+    if (!(!pMP1->isBad() && !pMP2->isBad() && i2 >= 0)) continue;
+    float X[3];
+    world_pos(pMP1->GetWorldPos(), X);
+    opt.x1w.insert(opt.x1w.end(), X, X + 3);
+    world_pos(pMP2->GetWorldPos(), X);
+    opt.x2w.insert(opt.x2w.end(), X, X + 3);
+    const auto kp1 = pKF1->GetKeyPointUn(i);
+    const auto kp2 = pKF2->GetKeyPointUn(i2);
+    static_assert(sizeof(kp1) == sizeof(uvo_keypoint), "keypoint layout must be cv::KeyPoint");
+    const uvo_keypoint& k1 = reinterpret_cast<const uvo_keypoint&>(kp1);
+    const uvo_keypoint& k2 = reinterpret_cast<const uvo_keypoint&>(kp2);
+    opt.obs1.push_back(k1.x), opt.obs1.push_back(k1.y);
+    opt.obs2.push_back(k2.x), opt.obs2.push_back(k2.y);
+    opt.info1.push_back(pKF1->GetInvSigma2(k1.octave));
+    opt.info2.push_back(pKF2->GetSigma2(k2.octave));  // :2781: the variance, as the reference passes it
+    opt.index.push_back((int32_t)i);
+  }
+}
+}  // namespace detail
+
 namespace Optimizer {
+
+// The candidates of one ComputeSim3 in ONE device call: candidate j is (pKF1, vpKF2[j], vvpMatches1[j], vS12[j]); vnInliers[j] is what
+// the reference's OptimizeSim3 returns for it.  Every candidate is treated as the single call treats it: its matches nulled, its S12
+// written unless it returned early.  Returns 0, or -1 when the library call fails (nothing of the caller's is then touched, vnInliers
+// included).
+template <class KF, class MP>
+int OptimizeSim3(Sim3Optimizer& opt, KF* pKF1, const std::vector<KF*>& vpKF2, std::vector<std::vector<MP*> >& vvpMatches1, std::vector<Sim3>& vS12,
+                 float th2, std::vector<int>& vnInliers) {
+  const int P = (int)vpKF2.size();
+  if (!opt.ok() || (int)vvpMatches1.size() != P || (int)vS12.size() != P) return -1;
+  opt.x1w.clear(), opt.x2w.clear(), opt.obs1.clear(), opt.obs2.clear(), opt.info1.clear(), opt.info2.clear(), opt.index.clear(), opt.offset.clear();
+  for (int j = 0; j < P; ++j) {
+    opt.offset.push_back((int32_t)opt.index.size());
+    detail::gather_sim3(opt, pKF1, vpKF2[j], vvpMatches1[j]);
+  }
+  opt.offset.push_back((int32_t)opt.index.size());
+  opt.removed.assign(opt.index.size() + 1, 0);
+  opt.problems.assign(P, uvo_sim3_opt_problem());
+  opt.results.assign(P, uvo_sim3_opt_result());
+  for (int j = 0; j < P; ++j) {
+    uvo_sim3_opt_problem& p = opt.problems[j];
+    const int off = opt.offset[j], n = opt.offset[j + 1] - off;
+    p.n = n, p.th2 = th2;
+    if (n) {
+      p.x1w = &opt.x1w[3 * off], p.x2w = &opt.x2w[3 * off], p.obs1 = &opt.obs1[2 * off], p.obs2 = &opt.obs2[2 * off];
+      p.info1 = &opt.info1[off], p.info2 = &opt.info2[off];
+    }
+    detail::keyframe_of(pKF1, p.kf1);
+    detail::keyframe_of(vpKF2[j], p.kf2);
+    for (int e = 0; e < 9; ++e) p.R12[e] = vS12[j].start_rotation()[e];
+    for (int e = 0; e < 3; ++e) p.t12[e] = vS12[j].start_translation()[e];
+    p.s12 = vS12[j].start_scale();
+    opt.results[j].removed = &opt.removed[off], opt.results[j].removed_cap = n;
+  }
+  if (P > 0 && uvo_sim3_optimize(opt.handle(), &opt.problems[0], P, &opt.results[0]) != UVO_OK) return -1;
+  vnInliers.assign(P, 0);
+  for (int j = 0; j < P; ++j) {
+    const uvo_sim3_opt_result& r = opt.results[j];
+    const int off = opt.offset[j], n = opt.offset[j + 1] - off;
+    for (int e = 0; e < n; ++e)
+      if (opt.removed[off + e]) vvpMatches1[j][opt.index[off + e]] = static_cast<MP*>(0);
+    if (r.more_iterations != 0) vS12[j] = Sim3(r.q, r.t, r.s);  // the early return runs no second round and leaves g2oS12 as it was
+    vnInliers[j] = r.n_inliers;
+  }
+  return 0;
+}
+
+// int Optimizer::OptimizeSim3(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches1, g2o::Sim3& g2oS12, float th2).  Returns
+// nIn, 0 on the early return, or -1 when the library call fails (nothing is then touched).
+template <class KF, class MP>
+int OptimizeSim3(Sim3Optimizer& opt, KF* pKF1, KF* pKF2, std::vector<MP*>& vpMatches1, Sim3& S12, float th2) {
+  std::vector<KF*> kfs(1, pKF2);
+  std::vector<std::vector<MP*> > matches(1);
+  matches[0].swap(vpMatches1);
+  std::vector<Sim3> sims(1, S12);
+  std::vector<int> inl;
+  const int rc = OptimizeSim3(opt, pKF1, kfs, matches, sims, th2, inl);
+  vpMatches1.swap(matches[0]);
+  if (rc != 0) return -1;
+  S12 = sims[0];
+  return inl[0];
+}
+
 
 // int Optimizer::PoseOptimization(Frame* pFrame).  Returns nInitialCorrespondences - nBad, or -1 when the library call fails (the
 // frame is then as the gathering left it: mvbOutlier cleared for the indices with a map point, the pose untouched).

@@ -1198,6 +1198,83 @@ int uvo_sim3solver_find(uvo_sim3solver_set* s, int id, uvo_glibc_rand* rng, uvo_
  * (zeros where the transform is not finite), counts [cap].  *n = hypotheses written (0 for an untouched solver). */
 int uvo_sim3solver_hypotheses(uvo_sim3solver_set* s, int id, int32_t* subsets, float* T12, float* T21, int32_t* counts, int cap, int* n);
 
+/* ------------------------------------------------------------------------------------------------
+ * Sim3 optimisation -- replaces Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2) (src/Optimizer.cc:2660-2856) and the
+ * parts of g2o it runs, the third step of LoopClosing::ComputeSim3 per loop candidate (src/LoopClosing.cc:463): one 7-DoF vertex,
+ * n fixed point pairs, per pair the edge through the similarity (EdgeSim3ProjectXYZ) and the edge through its inverse
+ * (EdgeInverseSim3ProjectXYZ), both with BaseBinaryEdge's NUMERIC Jacobian (central difference, delta 1e-9), the Huber kernel at
+ * sqrt(th2); optimize(5), the inlier check, then optimize(10) when a pair was bad, else optimize(5).  The candidates are independent
+ * until one succeeds, so ONE call optimises a list of them -- one upload, one launch (one workgroup per problem, both rounds), one
+ * download, nothing allocated -- and the caller takes the first in candidate order with n_inliers >= 10 (:465).
+ * The caller gathers each problem by walking vpMatches1 as :2713-2792 does.  Semantics are pinned to the reference's sources by
+ * tests/sim3opt_model.py: the state is g2o::Sim3 in double, its quaternion built from the float R12 and NEVER normalised; the update is
+ * Sim3(dx) * estimate with the four-branch exponential; lambda, ni and the stall count are set anew in each round, the estimate is
+ * not; a pair is bad when the chi2 of either STORED error (that of the last evaluated trial, accepted or not) exceeds th2; a bad pair
+ * of the first check is removed for good; a NaN chi2 satisfies neither comparison, so that pair stays and counts as an inlier; when
+ * fewer than 10 pairs survive the first check the call returns 0 inliers and the estimate is the input's (its round trip through the
+ * quaternion), as the reference returns 0 without writing g2oS12.
+ * The weights are taken as given.  The reference passes GetInvSigma2(octave1) for the first edge and GetSigma2(octave2) -- the
+ * variance, not its inverse -- for the second (:2781); an adaptor that wants the reference's behaviour passes exactly that.
+ * Departures from the reference; parity with a built g2o is not pinned, g2o not being available to the project:
+ *   - sums over the pairs are reduced in a fixed tree over 256 lanes, e12 before e21 within a pair, not serially in edge order;
+ *   - the 7 x 7 solve is an unpivoted LDL^T that fails unless every pivot is finite and > 0 (Eigen's LDLT pivots and accepts
+ *     semi-definite matrices); a failed solve makes the trial's chi2 DBL_MAX, as in the reference;
+ *   - sin, cos and exp are the library's own (2^-51); a step with |omega| > 7 rad or |sigma| > 40 gives a NaN trial, which is rejected;
+ *   - map() multiplies by one matrix s R per similarity where g2o rotates every point by the quaternion.
+ * The numeric Jacobian amplifies those roundings by 5e8: agreement with the model is to a tolerance (T, M of DESIGN.md), agreement
+ * between the device and the host build of the same source is bit for bit.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct uvo_sim3_optimizer uvo_sim3_optimizer;
+
+typedef struct uvo_sim3_opt_problem {
+  const float* x1w;        /* [n][3] GetWorldPos() of pMP1 (the map point of key i of pKF1) */
+  const float* x2w;        /* [n][3] GetWorldPos() of pMP2 = vpMatches1[i] */
+  const float* obs1;       /* [n][2] pKF1->GetKeyPointUn(i).pt */
+  const float* obs2;       /* [n][2] pKF2->GetKeyPointUn(i2).pt */
+  const float* info1;      /* [n]    information of e12: the reference passes pKF1->GetInvSigma2(octave1) */
+  const float* info2;      /* [n]    information of e21: the reference passes pKF2->GetSigma2(octave2), the variance (:2781) */
+  int32_t n;               /* nCorrespondences, 0..max_pairs */
+  float th2;
+  uvo_sim3_keyframe kf1, kf2; /* the library applies Rcw X + tcw on the host, in float as the reference's cv::Mat product */
+  float R12[9], t12[3], s12;  /* the start: g2oS12 as Sim3(R, t, s) is built from the solver's floats */
+  int32_t pad_;
+} uvo_sim3_opt_problem;
+
+typedef struct uvo_sim3_opt_result {
+  double q[4], t[3], s;    /* the estimate: quaternion x y z w (not normalised), translation, scale */
+  float R12[9], t12[3], scale; /* the same rounded to float: rotation().toRotationMatrix(), translation(), scale() */
+  int32_t n_inliers;       /* the return value; 0 on the early return, the estimate is then the input's round trip */
+  int32_t n_correspondences; /* n */
+  int32_t n_bad;           /* nBad of the first check */
+  int32_t more_iterations; /* iterations asked of the second optimize(): 5 or 10; 0 on the early return, which runs none */
+  int32_t removed_cap;     /* length of removed: UVO_E_CAPACITY when smaller than n */
+  uint8_t* removed;        /* caller's [n]: 1 where the reference nulls vpMatches1[idx] in either check; may be NULL */
+} uvo_sim3_opt_result;
+
+/* test tap: what the Levenberg driver saw; trials are uvo_pose_trace_trial records */
+typedef struct uvo_sim3_opt_trace_lin {
+  int32_t round, iteration;
+  double H[28];            /* upper triangle, row-major, before lambda */
+  double b[7];
+  double chi2;             /* activeRobustChi2 at the linearisation */
+} uvo_sim3_opt_trace_lin;
+typedef struct uvo_sim3_opt_trace {
+  int32_t n_lin, n_trials;
+  double q[4], t[3], s;    /* the final estimate in double */
+  uvo_sim3_opt_trace_lin lin[15];
+  uvo_pose_trace_trial trial[150];
+} uvo_sim3_opt_trace;
+
+/* max_problems 1..64, max_pairs 1..16384 (UVO_E_BADARG otherwise).  The set lives on a uvo_matcher handle (the loop-closing thread's
+ * stream, as the Sim3Solver set) and must be destroyed before it. */
+int uvo_sim3_optimizer_create(uvo_matcher* m, int max_problems, int max_pairs, uvo_sim3_optimizer** out);
+void uvo_sim3_optimizer_destroy(uvo_sim3_optimizer* o);
+/* results[j] answers problems[j].  UVO_E_CAPACITY: n_problems > max_problems, an n > max_pairs, a removed mask shorter than n.
+ * UVO_E_BADARG: null pointers, negative counts.  Nothing is written on an error.  n_problems == 0 is a no-op. */
+int uvo_sim3_optimize(uvo_sim3_optimizer* o, const uvo_sim3_opt_problem* problems, int n_problems, uvo_sim3_opt_result* results);
+/* test tap: the trace of problem `problem` of the set's last call (UVO_E_BADARG when the last call had no such problem). */
+int uvo_sim3_optimizer_trace(uvo_sim3_optimizer* o, int problem, uvo_sim3_opt_trace* out);
+
 /*
  * Initializer -- replaces USLAM::Initializer (include/Initializer.h, src/Initializer.cc) as Tracking::Initialize (src/Tracking.cc:1340)
  * and the recovery path (:1582) use it: the constructor on the reference frame, then Initialize(current frame, matches) until it

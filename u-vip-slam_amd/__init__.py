@@ -48,6 +48,7 @@ ABI_SYMBOLS = [
     "uvo_pose_optimizer_create", "uvo_pose_optimizer_destroy", "uvo_pose_optimize", "uvo_pose_optimizer_trace",
     "uvo_sim3solver_set_create", "uvo_sim3solver_set_destroy", "uvo_sim3solver_set_clear", "uvo_sim3solver_add", "uvo_sim3solver_set_ransac_parameters",
     "uvo_sim3solver_query", "uvo_sim3solver_iterate", "uvo_sim3solver_find", "uvo_sim3solver_hypotheses",
+    "uvo_sim3_optimizer_create", "uvo_sim3_optimizer_destroy", "uvo_sim3_optimize", "uvo_sim3_optimizer_trace",
     "uvo_initializer_create", "uvo_initializer_destroy", "uvo_initializer_set_reference", "uvo_initializer_initialize", "uvo_initializer_hypotheses",
     "uvo_kfdb_create", "uvo_kfdb_destroy", "uvo_kfdb_add", "uvo_kfdb_erase", "uvo_kfdb_clear", "uvo_kfdb_set_covisibles", "uvo_kfdb_detect_reloc",
     "uvo_kfdb_detect_loop", "uvo_kfdb_detect_loop_haloc", "uvo_kfdb_last_query", "uvo_kfdb_last_haloc", "uvo_kfdb_state", "uvo_kfdb_size",
@@ -285,6 +286,11 @@ def _load():
     lib.uvo_pose_optimizer_destroy.restype = None
     lib.uvo_pose_optimize.argtypes = [vp, vp, ci, vp]
     lib.uvo_pose_optimizer_trace.argtypes = [vp, ci, vp]
+    lib.uvo_sim3_optimizer_create.argtypes = [vp, ci, ci, vp]
+    lib.uvo_sim3_optimizer_destroy.argtypes = [vp]
+    lib.uvo_sim3_optimizer_destroy.restype = None
+    lib.uvo_sim3_optimize.argtypes = [vp, vp, ci, vp]
+    lib.uvo_sim3_optimizer_trace.argtypes = [vp, ci, vp]
     lib.uvo_sim3solver_set_create.argtypes = [vp, ci, ci, vp]
     lib.uvo_sim3solver_set_destroy.argtypes = [vp]
     lib.uvo_sim3solver_set_destroy.restype = None
@@ -1706,6 +1712,115 @@ class Sim3SolverSet:
         if rc:
             raise UvoError(rc, "uvo_sim3solver_hypotheses")
         return sub[:n.value].copy(), t12[:n.value].copy(), t21[:n.value].copy(), cnt[:n.value].copy()
+
+
+class Sim3OptProblemC(ctypes.Structure):
+    """uvo_sim3_opt_problem."""
+    _fields_ = [("x1w", ctypes.c_void_p), ("x2w", ctypes.c_void_p), ("obs1", ctypes.c_void_p), ("obs2", ctypes.c_void_p), ("info1", ctypes.c_void_p),
+                ("info2", ctypes.c_void_p), ("n", ctypes.c_int32), ("th2", ctypes.c_float), ("kf1", Sim3KeyFrame), ("kf2", Sim3KeyFrame),
+                ("R12", ctypes.c_float * 9), ("t12", ctypes.c_float * 3), ("s12", ctypes.c_float), ("pad_", ctypes.c_int32)]
+
+
+class Sim3OptResultC(ctypes.Structure):
+    """uvo_sim3_opt_result."""
+    _fields_ = [("q", ctypes.c_double * 4), ("t", ctypes.c_double * 3), ("s", ctypes.c_double), ("R12", ctypes.c_float * 9), ("t12", ctypes.c_float * 3),
+                ("scale", ctypes.c_float), ("n_inliers", ctypes.c_int32), ("n_correspondences", ctypes.c_int32), ("n_bad", ctypes.c_int32),
+                ("more_iterations", ctypes.c_int32), ("removed_cap", ctypes.c_int32), ("removed", ctypes.c_void_p)]
+
+
+class Sim3OptTraceLin(ctypes.Structure):
+    """uvo_sim3_opt_trace_lin."""
+    _fields_ = [("round", ctypes.c_int32), ("iteration", ctypes.c_int32), ("H", ctypes.c_double * 28), ("b", ctypes.c_double * 7), ("chi2", ctypes.c_double)]
+
+
+class Sim3OptTraceC(ctypes.Structure):
+    """uvo_sim3_opt_trace."""
+    _fields_ = [("n_lin", ctypes.c_int32), ("n_trials", ctypes.c_int32), ("q", ctypes.c_double * 4), ("t", ctypes.c_double * 3), ("s", ctypes.c_double),
+                ("lin", Sim3OptTraceLin * 15), ("trial", PoseTraceTrial * 150)]
+
+
+SIM3OPT_LIN_DTYPE = np.dtype([("round", "<i4"), ("iteration", "<i4"), ("H", "<f8", 28), ("b", "<f8", 7), ("chi2", "<f8")])
+
+
+class Sim3OptTrace:
+    """The test tap of one problem: q float64[4] (x y z w), t float64[3], s, lin (SIM3OPT_LIN_DTYPE, one record per linearisation), trial
+    (POSE_TRIAL_DTYPE, one per Levenberg trial)."""
+
+    def __init__(self, c):
+        self.q, self.t, self.s = np.array(c.q, np.float64), np.array(c.t, np.float64), float(c.s)
+        self.lin = np.frombuffer(bytes(c.lin), SIM3OPT_LIN_DTYPE)[:c.n_lin].copy()
+        self.trial = np.frombuffer(bytes(c.trial), POSE_TRIAL_DTYPE)[:c.n_trials].copy()
+
+
+class Sim3OptResult:
+    """One optimised candidate: q float64[4] (x y z w, not normalised), t float64[3], s; R12 float32[3, 3], t12 float32[3], scale;
+    n_inliers (the reference's return value; 0 on the early return, the estimate is then the input's), n_correspondences, n_bad,
+    more_iterations, removed uint8[n] (1 where the reference nulls vpMatches1[idx])."""
+
+    def __init__(self, c, removed):
+        self.q, self.t, self.s = np.array(c.q, np.float64), np.array(c.t, np.float64), float(c.s)
+        self.R12, self.t12, self.scale = np.array(c.R12, np.float32).reshape(3, 3), np.array(c.t12, np.float32), np.float32(c.scale)
+        self.n_inliers, self.n_correspondences, self.n_bad, self.more_iterations = c.n_inliers, c.n_correspondences, c.n_bad, c.more_iterations
+        self.removed = removed
+
+
+class Sim3Optimizer:
+    """Optimizer::OptimizeSim3 (src/Optimizer.cc:2660-2856) on an ORBmatcher handle: optimize() takes the problems of all loop candidates
+    and runs them as one device call; the caller takes the first in candidate order with n_inliers >= 10.  `_api` exists so that the
+    tests can drive another build through this class."""
+
+    def __init__(self, matcher, max_problems=1, max_pairs=4096, _api=None):
+        self._api = _api if _api is not None else lib
+        self._matcher = matcher   # the set launches in the handle's stream: keep it alive
+        self._h = ctypes.c_void_p()
+        self.max_problems, self.max_pairs = max_problems, max_pairs
+        rc = self._api.uvo_sim3_optimizer_create(matcher._h if matcher is not None else None, max_problems, max_pairs, ctypes.byref(self._h))
+        if rc:
+            self._h = None
+            raise UvoError(rc, "uvo_sim3_optimizer_create")
+
+    def close(self):
+        if getattr(self, "_h", None) and self._api is not None:
+            self._api.uvo_sim3_optimizer_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def optimize(self, problems, removed_cap=None):
+        """problems: a list of dicts x1w [n, 3], x2w [n, 3], obs1 [n, 2], obs2 [n, 2], info1 [n] (the reference: GetInvSigma2(octave1)),
+        info2 [n] (the reference: GetSigma2(octave2)), kf1 and kf2 = (Rcw, tcw, K) or Sim3KeyFrame, R12 [3, 3], t12 [3], s12, th2
+        -> a list of Sim3OptResult.  removed_cap (for the tests): the mask capacity passed for every problem instead of its n."""
+        cp = (Sim3OptProblemC * max(len(problems), 1))()
+        cr = (Sim3OptResultC * max(len(problems), 1))()
+        keep, masks = [], []
+        for j, p in enumerate(problems):
+            arr = [np.ascontiguousarray(p[k], np.float32).reshape(-1, w) for k, w in (("x1w", 3), ("x2w", 3), ("obs1", 2), ("obs2", 2), ("info1", 1), ("info2", 1))]
+            n = len(arr[0])
+            if any(len(a) != n for a in arr):
+                raise ValueError("the arrays of a problem differ in length")
+            m = np.zeros(max(n, 1), np.uint8)
+            keep.append(arr)
+            masks.append(m)
+            c = cp[j]
+            c.x1w, c.x2w, c.obs1, c.obs2, c.info1, c.info2 = [a.ctypes.data for a in arr]
+            c.n, c.th2 = n, float(np.float32(p["th2"]))
+            c.kf1, c.kf2 = [k if isinstance(k, Sim3KeyFrame) else Sim3KeyFrame.make(*k) for k in (p["kf1"], p["kf2"])]
+            c.R12 = (ctypes.c_float * 9)(*np.asarray(p["R12"], np.float32).reshape(9).tolist())
+            c.t12 = (ctypes.c_float * 3)(*np.asarray(p["t12"], np.float32).reshape(3).tolist())
+            c.s12 = float(np.float32(p["s12"]))
+            cr[j].removed, cr[j].removed_cap = m.ctypes.data, n if removed_cap is None else removed_cap
+        rc = self._api.uvo_sim3_optimize(self._h, cp, len(problems), cr)
+        if rc:
+            raise UvoError(rc, "uvo_sim3_optimize")
+        return [Sim3OptResult(cr[j], masks[j][:cp[j].n].copy()) for j in range(len(problems))]
+
+    def trace(self, problem=0):
+        """Test tap: Sim3OptTrace of problem `problem` of the last optimize() call."""
+        c = Sim3OptTraceC()
+        rc = self._api.uvo_sim3_optimizer_trace(self._h, problem, ctypes.byref(c))
+        if rc:
+            raise UvoError(rc, "uvo_sim3_optimizer_trace")
+        return Sim3OptTrace(c)
 
 
 class InitializerResultC(ctypes.Structure):
