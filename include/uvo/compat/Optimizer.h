@@ -17,7 +17,27 @@
 //
 // and an overload over the list of candidates that issues ONE device call; the caller takes the first candidate in order with
 // nInliers >= 10.  With it the path from loop candidate to accepted loop links nothing of the reference's Optimizer.  The IMU overloads
-// of PoseOptimization (:319, :779), OptimizeEssentialGraph and the bundle adjustments stay with the reference's Optimizer.
+// of PoseOptimization (:319, :779), OptimizeEssentialGraph and the NavState bundle adjustments stay with the reference's Optimizer.
+//
+// Optimizer::LocalBundleAdjustment(pKF, pbStopFlag, pMap, pLM) (src/Optimizer.cc:2147-2405, called at src/LocalMapping.cc:807) and
+// Optimizer::BundleAdjustment / GlobalBundleAdjustemnt / RecoveryBundleAdjustemnt (:1879-2010, src/Tracking.cc:1480, :1807) over the C
+// ABI's bundle adjuster (uvo_bundle_adjust* in uvo/uvo.h):
+//
+//     - Optimizer::LocalBundleAdjustment(mpCurrentKeyFrame, &mbAbortBA, mpMap, this);
+//     + USLAM::Optimizer::LocalBundleAdjustment(mpCurrentKeyFrame, &mbAbortBA, mpMap, this, adjuster);   // a USLAM::BundleAdjuster
+//
+// They need of the key-frame type mnId, mnBALocalForKF, mnBAFixedForKF, isBad(), GetVectorCovisibleKeyFrames(), GetMapPointMatches(),
+// GetRotation() and GetTranslation() (the floats of GetPose()), GetKeyPointUn(i), GetInvSigma2(octave), fx, fy, cx, cy,
+// EraseMapPointMatch(pMP) and EraseMapPointMatch(idx); of the map-point type mnBALocalForKF, isBad(), GetObservations() (a
+// std::map<KF*, size_t>), GetWorldPos(), EraseObservation(pKF), GetIndexInKeyFrame(pKF), UpdateNormalAndDepth(); of the map
+// mMutexMapUpdate (lock() / unlock()), GetAllKeyFrames(), GetAllMapPoints(); of the local mapper SetMapUpdateFlagInTracking(bool).
+// Poses and positions are written through USLAM::ba_set_pose(pKF, const float T[16]) and USLAM::ba_set_world_pos(pMP, const float
+// X[3]), whose defaults call pKF->SetPose(T) and pMP->SetWorldPos(X) with the float pointers: a cv::Mat host overloads the two (wrap
+// the floats in a cv::Mat header and clone).  The reference's effects are kept: the gathering of :2149-2198 with both marks, a
+// point's edges in the order its GetObservations() iterates, the erasures of both checks, SetPose / SetWorldPos /
+// UpdateNormalAndDepth and the map-update flag.  Departures: pbStopFlag is read once, before the call (1 is returned and nothing is
+// optimised when it is set); the erasures of the first check and the write-back happen once, after the call and under
+// mMutexMapUpdate, not in between the two rounds.
 //
 // The frame type needs mvpMapPoints (pointers; null where there is no map point; GetWorldPos() returning something with at<float>(i)
 // or operator[]), mvKeysUn (cv::KeyPoint layout), mvInvLevelSigma2, mvbOutlier (std::vector<bool> or anything indexable and
@@ -37,6 +57,7 @@
 #ifndef UVO_COMPAT_OPTIMIZER_H_
 #define UVO_COMPAT_OPTIMIZER_H_
 #include <cmath>
+#include <type_traits>
 #include <vector>
 
 #include "uvo/uvo.h"
@@ -234,6 +255,109 @@ void gather_sim3(Sim3Optimizer& opt, KF* pKF1, KF* pKF2, const std::vector<MP*>&
 }
 }  // namespace detail
 
+// the owner of the device adjuster: one on the mapping thread's matcher handle
+class BundleAdjuster {
+ public:
+  BundleAdjuster(uvo_matcher* m, int max_free, int max_fixed, int max_points, int max_edges) : a_(0) {
+    uvo_bundle_adjuster_create(m, max_free, max_fixed, max_points, max_edges, &a_);
+  }
+  ~BundleAdjuster() { uvo_bundle_adjuster_destroy(a_); }
+  bool ok() const { return a_ != 0; }
+  uvo_bundle_adjuster* handle() { return a_; }
+  // gathering buffers, kept between calls so that a call allocates nothing once they have grown
+  std::vector<float> Tcw, points, obs, inv_sigma2, cameras, Tcw_out, points_out;
+  std::vector<uint8_t> fixed, point_bad, removed1, removed2;
+  std::vector<int32_t> begin, edge_kf, edge_camera, edge_index;  // edge_index: the observation's index in its key frame
+  uvo_ba_result result;                                          // of the last call: counts, iterations, trials
+
+ private:
+  BundleAdjuster(const BundleAdjuster&);
+  BundleAdjuster& operator=(const BundleAdjuster&);
+  uvo_bundle_adjuster* a_;
+};
+
+template <class KF>
+void ba_set_pose(KF* pKF, const float T[16]) {
+  pKF->SetPose(T);
+}
+template <class MP>
+void ba_set_world_pos(MP* pMP, const float X[3]) {
+  pMP->SetWorldPos(X);
+}
+
+namespace detail {
+template <class M>
+struct LockGuard {
+  explicit LockGuard(M& m) : m_(m) { m_.lock(); }
+  ~LockGuard() { m_.unlock(); }
+  M& m_;
+};
+inline void ba_clear(BundleAdjuster& a) {
+  a.Tcw.clear(), a.points.clear(), a.obs.clear(), a.inv_sigma2.clear(), a.cameras.clear(), a.fixed.clear(), a.point_bad.clear();
+  a.begin.assign(1, 0), a.edge_kf.clear(), a.edge_camera.clear(), a.edge_index.clear();
+}
+template <class KF>
+void ba_add_keyframe(BundleAdjuster& a, KF* pKF, bool fixed) {
+  const auto R = pKF->GetRotation();
+  const auto t = pKF->GetTranslation();
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) a.Tcw.push_back(mat_elem(R, 3 * r + c, 0));
+    a.Tcw.push_back(mat_elem(t, r, 0));
+  }
+  a.fixed.push_back(fixed ? 1 : 0);
+}
+template <class KF>
+int ba_camera(BundleAdjuster& a, KF* pKF) {
+  const float k[4] = {(float)pKF->fx, (float)pKF->fy, (float)pKF->cx, (float)pKF->cy};
+  const int n = (int)a.cameras.size() / 4;
+  for (int i = 0; i < n; ++i)
+    if (a.cameras[4 * i] == k[0] && a.cameras[4 * i + 1] == k[1] && a.cameras[4 * i + 2] == k[2] && a.cameras[4 * i + 3] == k[3]) return i;
+  a.cameras.insert(a.cameras.end(), k, k + 4);
+  return n;
+}
+// a point and its edges (:2261-2307, :1934-1978): the observations in the order GetObservations() iterates, those of bad key frames and
+// of key frames that are no vertex skipped.  edge_kfs receives the key frame of every edge.
+template <class KF, class MP>
+void ba_add_point(BundleAdjuster& a, MP* pMP, const std::vector<KF*>& vertices, std::vector<KF*>& edge_kfs) {
+  float X[3];
+  world_pos(pMP->GetWorldPos(), X);
+  a.points.insert(a.points.end(), X, X + 3);
+  a.point_bad.push_back(pMP->isBad() ? 1 : 0);
+  const auto observations = pMP->GetObservations();
+  for (auto mit = observations.begin(); mit != observations.end(); ++mit) {
+    KF* pKFi = mit->first;
+    if (pKFi->isBad()) continue;
+    int k = -1;
+    for (size_t v = 0; v < vertices.size() && k < 0; ++v)
+      if (vertices[v] == pKFi) k = (int)v;
+    if (k < 0) continue;
+    const auto kp = pKFi->GetKeyPointUn(mit->second);
+    static_assert(sizeof(kp) == sizeof(uvo_keypoint), "keypoint layout must be cv::KeyPoint");
+    const uvo_keypoint& u = reinterpret_cast<const uvo_keypoint&>(kp);
+    a.edge_kf.push_back(k), a.obs.push_back(u.x), a.obs.push_back(u.y);
+    a.inv_sigma2.push_back(pKFi->GetInvSigma2(u.octave));
+    a.edge_camera.push_back(ba_camera(a, pKFi));
+    a.edge_index.push_back((int32_t)mit->second);
+    edge_kfs.push_back(pKFi);
+  }
+  a.begin.push_back((int32_t)a.edge_kf.size());
+}
+inline int ba_call(BundleAdjuster& a, int mode, int n_iterations) {
+  const size_t K = a.fixed.size(), P = a.point_bad.size(), E = a.edge_kf.size();
+  a.Tcw_out.assign(16 * K + 1, 0.f), a.points_out.assign(3 * P + 1, 0.f), a.removed1.assign(E + 1, 0), a.removed2.assign(E + 1, 0);
+  a.Tcw.push_back(0.f), a.points.push_back(0.f), a.obs.push_back(0.f), a.inv_sigma2.push_back(0.f), a.cameras.push_back(0.f);
+  a.fixed.push_back(0), a.point_bad.push_back(0), a.edge_kf.push_back(0), a.edge_camera.push_back(0);  // no empty vector is indexed
+  uvo_ba_problem q = uvo_ba_problem();
+  q.mode = mode, q.n_iterations = n_iterations;
+  q.n_keyframes = (int32_t)K, q.n_points = (int32_t)P, q.n_edges = (int32_t)E, q.n_cameras = (int32_t)(a.cameras.size() / 4);
+  q.kf_Tcw = &a.Tcw[0], q.kf_fixed = &a.fixed[0], q.points = &a.points[0], q.point_bad = &a.point_bad[0], q.point_edge_begin = &a.begin[0];
+  q.edge_kf = &a.edge_kf[0], q.edge_obs = &a.obs[0], q.edge_inv_sigma2 = &a.inv_sigma2[0], q.edge_camera = &a.edge_camera[0], q.cameras = &a.cameras[0];
+  a.result = uvo_ba_result();
+  a.result.kf_Tcw = &a.Tcw_out[0], a.result.points = &a.points_out[0], a.result.removed1 = &a.removed1[0], a.result.removed2 = &a.removed2[0];
+  return a.ok() && uvo_bundle_adjust(a.handle(), &q, &a.result) == UVO_OK ? 0 : -1;
+}
+}  // namespace detail
+
 namespace Optimizer {
 
 // The candidates of one ComputeSim3 in ONE device call: candidate j is (pKF1, vpKF2[j], vvpMatches1[j], vS12[j]); vnInliers[j] is what
@@ -331,6 +455,134 @@ int PoseOptimization(PoseOptimizer& opt, Frame* pFrame) {
   for (int j = 0; j < n; ++j) pFrame->mvbOutlier[opt.index[j]] = opt.outlier[j] != 0;
   for (int e = 0; e < 16; ++e) T[e] = r.Tcw[e];
   return r.n_inliers;
+}
+
+// void Optimizer::LocalBundleAdjustment(KeyFrame* pKF, bool* pbStopFlag, Map* pMap, LocalMapping* pLM).  Returns 0; 1 when *pbStopFlag
+// was set (the marks of the gathering are left, nothing else is touched); -1 when the library call fails (likewise).
+template <class KF, class Map, class LM>
+int LocalBundleAdjustment(KF* pKF, bool* pbStopFlag, Map* pMap, LM* pLM, BundleAdjuster& adj) {
+  typedef typename std::remove_pointer<typename std::remove_reference<decltype(pKF->GetMapPointMatches()[0])>::type>::type MP;
+  // Local KeyFrames: First Breath Search from Current Keyframe (:2149-2162)
+  std::vector<KF*> lLocalKeyFrames(1, pKF);
+  pKF->mnBALocalForKF = pKF->mnId;
+  const std::vector<KF*> vNeighKFs = pKF->GetVectorCovisibleKeyFrames();
+  for (int i = 0, iend = (int)vNeighKFs.size(); i < iend; i++) {
+    KF* pKFi = vNeighKFs[i];
+    pKFi->mnBALocalForKF = pKF->mnId;
+    if (!pKFi->isBad()) lLocalKeyFrames.push_back(pKFi);
+  }
+  // Local MapPoints seen in Local KeyFrames (:2164-2180)
+  std::vector<MP*> lLocalMapPoints;
+  for (size_t l = 0; l < lLocalKeyFrames.size(); ++l) {
+    const std::vector<MP*> vpMPs = lLocalKeyFrames[l]->GetMapPointMatches();
+    for (size_t v = 0; v < vpMPs.size(); ++v) {
+      MP* pMP = vpMPs[v];
+      if (pMP)
+        if (!pMP->isBad())
+          if (pMP->mnBALocalForKF != pKF->mnId) {
+            lLocalMapPoints.push_back(pMP);
+            pMP->mnBALocalForKF = pKF->mnId;
+          }
+    }
+  }
+  // Fixed Keyframes. Keyframes that see Local MapPoints but that are not Local Keyframes (:2182-2198)
+  std::vector<KF*> lFixedCameras;
+  for (size_t l = 0; l < lLocalMapPoints.size(); ++l) {
+    const auto observations = lLocalMapPoints[l]->GetObservations();
+    for (auto mit = observations.begin(); mit != observations.end(); ++mit) {
+      KF* pKFi = mit->first;
+      if (pKFi->mnBALocalForKF != pKF->mnId && pKFi->mnBAFixedForKF != pKF->mnId) {
+        pKFi->mnBAFixedForKF = pKF->mnId;
+        if (!pKFi->isBad()) lFixedCameras.push_back(pKFi);
+      }
+    }
+  }
+  if (pbStopFlag && *pbStopFlag) return 1;
+  detail::ba_clear(adj);
+  std::vector<KF*> vertices(lLocalKeyFrames);
+  vertices.insert(vertices.end(), lFixedCameras.begin(), lFixedCameras.end());
+  for (size_t l = 0; l < lLocalKeyFrames.size(); ++l) detail::ba_add_keyframe(adj, lLocalKeyFrames[l], lLocalKeyFrames[l]->mnId == 0);
+  for (size_t l = 0; l < lFixedCameras.size(); ++l) detail::ba_add_keyframe(adj, lFixedCameras[l], true);
+  std::vector<KF*> vpEdgeKF;
+  for (size_t l = 0; l < lLocalMapPoints.size(); ++l) detail::ba_add_point(adj, lLocalMapPoints[l], vertices, vpEdgeKF);
+  if (detail::ba_call(adj, UVO_BA_LOCAL, 0) != 0) return -1;
+  {
+    detail::LockGuard<decltype(pMap->mMutexMapUpdate)> lock(pMap->mMutexMapUpdate);
+    // Check inlier observations: the first check's erasures (:2316-2333), then the second's (:2361-2379)
+    for (size_t j = 0; j < lLocalMapPoints.size(); ++j) {
+      MP* pMP = lLocalMapPoints[j];
+      for (int e = adj.begin[j]; e < adj.begin[j + 1]; ++e)
+        if (adj.removed1[e]) {
+          vpEdgeKF[e]->EraseMapPointMatch(pMP);
+          pMP->EraseObservation(vpEdgeKF[e]);
+        }
+    }
+    for (size_t j = 0; j < lLocalMapPoints.size(); ++j) {
+      MP* pMP = lLocalMapPoints[j];
+      for (int e = adj.begin[j]; e < adj.begin[j + 1]; ++e)
+        if (adj.removed2[e]) {
+          vpEdgeKF[e]->EraseMapPointMatch(pMP->GetIndexInKeyFrame(vpEdgeKF[e]));
+          pMP->EraseObservation(vpEdgeKF[e]);
+        }
+    }
+    // Recover optimized data (:2381-2399)
+    for (size_t l = 0; l < lLocalKeyFrames.size(); ++l) ba_set_pose(lLocalKeyFrames[l], &adj.Tcw_out[16 * l]);
+    for (size_t j = 0; j < lLocalMapPoints.size(); ++j) {
+      ba_set_world_pos(lLocalMapPoints[j], &adj.points_out[3 * j]);
+      lLocalMapPoints[j]->UpdateNormalAndDepth();
+    }
+  }
+  if (pLM) pLM->SetMapUpdateFlagInTracking(true);
+  return 0;
+}
+
+// void Optimizer::BundleAdjustment(const vector<KeyFrame*>& vpKFs, const vector<MapPoint*>& vpMP, int nIterations, bool* pbStopFlag):
+// every key frame free but mnId == 0, one optimize(nIterations), no check, nothing erased.  Returns 0, 1 (stop flag set) or -1.
+template <class KF, class MP>
+int BundleAdjustment(const std::vector<KF*>& vpKFs, const std::vector<MP*>& vpMP, int nIterations, bool* pbStopFlag, BundleAdjuster& adj) {
+  if (pbStopFlag && *pbStopFlag) return 1;
+  detail::ba_clear(adj);
+  std::vector<KF*> vertices;
+  for (size_t i = 0; i < vpKFs.size(); i++) {
+    KF* pKF = vpKFs[i];
+    if (pKF->isBad()) continue;
+    vertices.push_back(pKF);
+    detail::ba_add_keyframe(adj, pKF, pKF->mnId == 0);
+  }
+  std::vector<MP*> points;
+  std::vector<KF*> vpEdgeKF;
+  for (size_t i = 0; i < vpMP.size(); i++) {
+    MP* pMP = vpMP[i];
+    if (!pMP || pMP->isBad()) continue;
+    points.push_back(pMP);
+    detail::ba_add_point(adj, pMP, vertices, vpEdgeKF);
+  }
+  if (detail::ba_call(adj, UVO_BA_FULL, nIterations) != 0) return -1;
+  // Recover optimized data (:1986-2008)
+  for (size_t l = 0; l < vertices.size(); ++l) ba_set_pose(vertices[l], &adj.Tcw_out[16 * l]);
+  for (size_t j = 0; j < points.size(); ++j) {
+    ba_set_world_pos(points[j], &adj.points_out[3 * j]);
+    points[j]->UpdateNormalAndDepth();
+  }
+  return 0;
+}
+
+// void Optimizer::GlobalBundleAdjustemnt(Map* pMap, int nIterations, bool* pbStopFlag), with the reference's spelling
+template <class Map>
+int GlobalBundleAdjustemnt(Map* pMap, int nIterations, bool* pbStopFlag, BundleAdjuster& adj) {
+  const auto vpKFs = pMap->GetAllKeyFrames();
+  const auto vpMP = pMap->GetAllMapPoints();
+  return BundleAdjustment(vpKFs, vpMP, nIterations, pbStopFlag, adj);
+}
+
+// void Optimizer::RecoveryBundleAdjustemnt(KeyFrame* pKFini, KeyFrame* pKFcur, int nIterations, bool* pbStopFlag)
+template <class KF>
+int RecoveryBundleAdjustemnt(KF* pKFini, KF* pKFcur, int nIterations, bool* pbStopFlag, BundleAdjuster& adj) {
+  std::vector<KF*> vpKFs;
+  vpKFs.push_back(pKFini);
+  vpKFs.push_back(pKFcur);
+  const auto vpMP = pKFcur->getmvpMappoints();
+  return BundleAdjustment(vpKFs, vpMP, nIterations, pbStopFlag, adj);
 }
 
 }  // namespace Optimizer

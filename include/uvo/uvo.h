@@ -1275,6 +1275,87 @@ int uvo_sim3_optimize(uvo_sim3_optimizer* o, const uvo_sim3_opt_problem* problem
 /* test tap: the trace of problem `problem` of the set's last call (UVO_E_BADARG when the last call had no such problem). */
 int uvo_sim3_optimizer_trace(uvo_sim3_optimizer* o, int problem, uvo_sim3_opt_trace* out);
 
+/* ------------------------------------------------------------------------------------------------
+ * Bundle adjustment -- replaces Optimizer::LocalBundleAdjustment(pKF, pbStopFlag, pMap, pLM) (src/Optimizer.cc:2147-2405, called at
+ * src/LocalMapping.cc:807) and Optimizer::BundleAdjustment(vpKFs, vpMP, nIterations, ...) (:1896-2010, behind
+ * GlobalBundleAdjustemnt and RecoveryBundleAdjustemnt) with the parts of g2o they run: VertexSE3Expmap key frames (a fixed one
+ * contributes no block), marginalised VertexSBAPointXYZ points, one EdgeSE3ProjectXYZ per observation with information
+ * invSigma2 * I and the Huber kernel at sqrt(5.991), BlockSolver's Schur complement rebuilt at every Levenberg trial, the Levenberg
+ * driver (tau 1e-5 on the largest diagonal entry over poses AND points, rho over the whole step, ten trials).
+ * UVO_BA_LOCAL: optimize(5); an edge is bad when the chi2 of its STORED error (that of the last evaluated trial, accepted or not)
+ * exceeds 5.991 or its depth at the current estimates is not positive; edges of points flagged point_bad are not examined; bad edges
+ * are removed for good; a point or key frame left without an edge drops out and keeps its estimate; optimize(10); the second check
+ * over the surviving edges.  UVO_BA_FULL: one optimize(n_iterations), no check.  Lambda and ni are set anew in each optimize(), the
+ * estimates are not.
+ * The phases of a call are separate launches in the handle's stream; the Levenberg decision is made on the device and the host reads
+ * one status word per trial and per optimize() (n_syncs of the result counts those reads and the download's synchronise: at most
+ * 2 + 150 + 1 in local mode).  Nothing is allocated per call.  C++ adaptors: uvo/compat/Optimizer.h.
+ * Departures from the reference; parity with a built g2o is not pinned, g2o not being available to the project:
+ *   - pbStopFlag is not honoured inside a call: an adaptor reads it before the call and returns without optimising when it is set;
+ *   - the reduced pose system is solved by a dense unpivoted LDL^T in key-frame order that fails unless every pivot is finite and > 0,
+ *     not by SimplicialLDLT under an AMD ordering; a failed solve makes the trial's chi2 DBL_MAX and the step keeps its last value;
+ *   - every sum has one fixed shape that depends on indices alone (csrc/ba_core.hpp), not g2o's order over its containers;
+ *   - sin and cos are the library's own (2^-51); a step with |omega| > 7 rad gives a NaN trial, which is rejected.
+ * Agreement with the model (tests/ba_model.py) is to a tolerance, agreement between the device and the host build of the same source
+ * (tests/emu/ba_emu.cpp) is bit for bit.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct uvo_bundle_adjuster uvo_bundle_adjuster;
+
+enum { UVO_BA_LOCAL = 0, UVO_BA_FULL = 1 };
+
+typedef struct uvo_ba_problem {
+  int32_t mode;            /* UVO_BA_LOCAL or UVO_BA_FULL */
+  int32_t n_iterations;    /* full mode: 1..32; ignored in local mode */
+  int32_t n_keyframes, n_points, n_edges, n_cameras;
+  const float* kf_Tcw;     /* [n_keyframes][12] rows of [R | t]; converted as Converter::toSE3Quat does */
+  const uint8_t* kf_fixed; /* [n_keyframes] 1: fixed.  The adaptor applies the mnId == 0 rule */
+  const float* points;     /* [n_points][3] */
+  const uint8_t* point_bad;/* [n_points] pMP->isBad() at the checks; may be NULL */
+  const int32_t* point_edge_begin; /* [n_points + 1] edges are grouped by point in the order the caller lists them */
+  const int32_t* edge_kf;  /* [n_edges] key-frame index */
+  const float* edge_obs;   /* [n_edges][2] */
+  const float* edge_inv_sigma2; /* [n_edges] */
+  const int32_t* edge_camera;   /* [n_edges] row of cameras */
+  const float* cameras;    /* [n_cameras][4] fx fy cx cy, 1..64 rows */
+} uvo_ba_problem;
+
+typedef struct uvo_ba_result {
+  double* kf_estimate;     /* [n_keyframes][7] quaternion x y z w and t; a fixed key frame's is its input's conversion; may be NULL */
+  float* kf_Tcw;           /* [n_keyframes][16] Converter::toCvMat of the estimate; may be NULL */
+  double* point_estimate;  /* [n_points][3]; may be NULL */
+  float* points;           /* [n_points][3]; may be NULL */
+  uint8_t* removed1;       /* [n_edges] 1 where the first check erases the observation; may be NULL */
+  uint8_t* removed2;       /* [n_edges] the second check; may be NULL */
+  int32_t n_removed1, n_removed2;
+  int32_t iterations[2];   /* linearisations run per optimize() */
+  int32_t n_trials, n_syncs;
+} uvo_ba_result;
+
+/* test tap: what the Levenberg driver saw; trials are uvo_pose_trace_trial records */
+typedef struct uvo_ba_trace_lin {
+  int32_t round, iteration;
+  int32_t n_edges, n_free, n_points, pad_; /* active edges, free key frames and points of the linearisation */
+  double chi2;             /* activeRobustChi2 at the linearisation */
+  double maxdiag;          /* the largest diagonal entry over poses and points */
+} uvo_ba_trace_lin;
+typedef struct uvo_ba_trace {
+  int32_t n_lin, n_trials;
+  uvo_ba_trace_lin lin[32];
+  uvo_pose_trace_trial trial[320];
+} uvo_ba_trace;
+
+/* max_free 1..64, max_fixed 0..256, max_points 1..32768, max_edges 1..262144 (UVO_E_BADARG otherwise).  The adjuster lives on a
+ * uvo_matcher handle (the mapping thread's stream, as uvo_create_new_map_points) and must be destroyed before it. */
+int uvo_bundle_adjuster_create(uvo_matcher* m, int max_free, int max_fixed, int max_points, int max_edges, uvo_bundle_adjuster** out);
+void uvo_bundle_adjuster_destroy(uvo_bundle_adjuster* a);
+/* UVO_E_CAPACITY: more free or fixed key frames, points or edges than the adjuster was sized for.  UVO_E_BADARG: null pointers,
+ * counts out of range, an edge naming a key frame or camera out of range, a point_edge_begin that does not ascend from 0 to n_edges,
+ * two edges of one point to one free key frame.  Nothing is written on an error.  A problem with no free key frame (or no edge) is
+ * answered with the inputs unchanged. */
+int uvo_bundle_adjust(uvo_bundle_adjuster* a, const uvo_ba_problem* problem, uvo_ba_result* result);
+/* test tap: the trace of the adjuster's last call (no record when that call optimised nothing). */
+int uvo_bundle_adjuster_trace(uvo_bundle_adjuster* a, uvo_ba_trace* out);
+
 /*
  * Initializer -- replaces USLAM::Initializer (include/Initializer.h, src/Initializer.cc) as Tracking::Initialize (src/Tracking.cc:1340)
  * and the recovery path (:1582) use it: the constructor on the reference frame, then Initialize(current frame, matches) until it

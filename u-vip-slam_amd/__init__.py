@@ -49,6 +49,7 @@ ABI_SYMBOLS = [
     "uvo_sim3solver_set_create", "uvo_sim3solver_set_destroy", "uvo_sim3solver_set_clear", "uvo_sim3solver_add", "uvo_sim3solver_set_ransac_parameters",
     "uvo_sim3solver_query", "uvo_sim3solver_iterate", "uvo_sim3solver_find", "uvo_sim3solver_hypotheses",
     "uvo_sim3_optimizer_create", "uvo_sim3_optimizer_destroy", "uvo_sim3_optimize", "uvo_sim3_optimizer_trace",
+    "uvo_bundle_adjuster_create", "uvo_bundle_adjuster_destroy", "uvo_bundle_adjust", "uvo_bundle_adjuster_trace",
     "uvo_initializer_create", "uvo_initializer_destroy", "uvo_initializer_set_reference", "uvo_initializer_initialize", "uvo_initializer_hypotheses",
     "uvo_kfdb_create", "uvo_kfdb_destroy", "uvo_kfdb_add", "uvo_kfdb_erase", "uvo_kfdb_clear", "uvo_kfdb_set_covisibles", "uvo_kfdb_detect_reloc",
     "uvo_kfdb_detect_loop", "uvo_kfdb_detect_loop_haloc", "uvo_kfdb_last_query", "uvo_kfdb_last_haloc", "uvo_kfdb_state", "uvo_kfdb_size",
@@ -291,6 +292,11 @@ def _load():
     lib.uvo_sim3_optimizer_destroy.restype = None
     lib.uvo_sim3_optimize.argtypes = [vp, vp, ci, vp]
     lib.uvo_sim3_optimizer_trace.argtypes = [vp, ci, vp]
+    lib.uvo_bundle_adjuster_create.argtypes = [vp, ci, ci, ci, ci, vp]
+    lib.uvo_bundle_adjuster_destroy.argtypes = [vp]
+    lib.uvo_bundle_adjuster_destroy.restype = None
+    lib.uvo_bundle_adjust.argtypes = [vp, vp, vp]
+    lib.uvo_bundle_adjuster_trace.argtypes = [vp, vp]
     lib.uvo_sim3solver_set_create.argtypes = [vp, ci, ci, vp]
     lib.uvo_sim3solver_set_destroy.argtypes = [vp]
     lib.uvo_sim3solver_set_destroy.restype = None
@@ -1821,6 +1827,126 @@ class Sim3Optimizer:
         if rc:
             raise UvoError(rc, "uvo_sim3_optimizer_trace")
         return Sim3OptTrace(c)
+
+
+UVO_BA_LOCAL, UVO_BA_FULL = 0, 1
+
+
+class BaProblemC(ctypes.Structure):
+    """uvo_ba_problem."""
+    _fields_ = [("mode", ctypes.c_int32), ("n_iterations", ctypes.c_int32), ("n_keyframes", ctypes.c_int32), ("n_points", ctypes.c_int32),
+                ("n_edges", ctypes.c_int32), ("n_cameras", ctypes.c_int32), ("kf_Tcw", ctypes.c_void_p), ("kf_fixed", ctypes.c_void_p),
+                ("points", ctypes.c_void_p), ("point_bad", ctypes.c_void_p), ("point_edge_begin", ctypes.c_void_p), ("edge_kf", ctypes.c_void_p),
+                ("edge_obs", ctypes.c_void_p), ("edge_inv_sigma2", ctypes.c_void_p), ("edge_camera", ctypes.c_void_p), ("cameras", ctypes.c_void_p)]
+
+
+class BaResultC(ctypes.Structure):
+    """uvo_ba_result."""
+    _fields_ = [("kf_estimate", ctypes.c_void_p), ("kf_Tcw", ctypes.c_void_p), ("point_estimate", ctypes.c_void_p), ("points", ctypes.c_void_p),
+                ("removed1", ctypes.c_void_p), ("removed2", ctypes.c_void_p), ("n_removed1", ctypes.c_int32), ("n_removed2", ctypes.c_int32),
+                ("iterations", ctypes.c_int32 * 2), ("n_trials", ctypes.c_int32), ("n_syncs", ctypes.c_int32)]
+
+
+class BaTraceLin(ctypes.Structure):
+    """uvo_ba_trace_lin."""
+    _fields_ = [("round", ctypes.c_int32), ("iteration", ctypes.c_int32), ("n_edges", ctypes.c_int32), ("n_free", ctypes.c_int32),
+                ("n_points", ctypes.c_int32), ("pad_", ctypes.c_int32), ("chi2", ctypes.c_double), ("maxdiag", ctypes.c_double)]
+
+
+class BaTraceC(ctypes.Structure):
+    """uvo_ba_trace."""
+    _fields_ = [("n_lin", ctypes.c_int32), ("n_trials", ctypes.c_int32), ("lin", BaTraceLin * 32), ("trial", PoseTraceTrial * 320)]
+
+
+BA_LIN_DTYPE = np.dtype([("round", "<i4"), ("iteration", "<i4"), ("n_edges", "<i4"), ("n_free", "<i4"), ("n_points", "<i4"), ("pad_", "<i4"),
+                         ("chi2", "<f8"), ("maxdiag", "<f8")])
+
+
+class BaTrace:
+    """The test tap of a call: lin (BA_LIN_DTYPE, one record per linearisation), trial (POSE_TRIAL_DTYPE, one per Levenberg trial)."""
+
+    def __init__(self, c):
+        self.lin = np.frombuffer(bytes(c.lin), BA_LIN_DTYPE)[:c.n_lin].copy()
+        self.trial = np.frombuffer(bytes(c.trial), POSE_TRIAL_DTYPE)[:c.n_trials].copy()
+
+
+class BaResult:
+    """One adjusted problem: kf_estimate float64[K, 7] (quaternion x y z w, t), kf_Tcw float32[K, 4, 4], point_estimate float64[P, 3],
+    points float32[P, 3], removed1 / removed2 uint8[E] (the observations the two checks erase), their counts, iterations (linearisations
+    per optimize()), n_trials, n_syncs."""
+
+    def __init__(self, c, arrays):
+        self.kf_estimate, self.kf_Tcw, self.point_estimate, self.points, self.removed1, self.removed2 = arrays
+        self.n_removed1, self.n_removed2, self.iterations = c.n_removed1, c.n_removed2, (c.iterations[0], c.iterations[1])
+        self.n_trials, self.n_syncs = c.n_trials, c.n_syncs
+
+
+def ba_marshal(scene, mode=UVO_BA_LOCAL, n_iterations=0):
+    """A scene dict (Tcw [K, 12] or [K, 3, 4], fixed [K], points [P, 3], point_bad [P] or absent, begin [P + 1], edge_kf [E],
+    edge_obs [E, 2], edge_inv_sigma2 [E], edge_camera [E], cameras [C, 4]) -> (BaProblemC, BaResultC, the result's arrays, what to keep alive)."""
+    f32, i32, u8 = np.float32, np.int32, np.uint8
+    T = np.ascontiguousarray(scene["Tcw"], f32).reshape(-1, 12)
+    fixed = np.ascontiguousarray(scene["fixed"], u8).reshape(-1)
+    pts = np.ascontiguousarray(scene["points"], f32).reshape(-1, 3)
+    bad = None if scene.get("point_bad") is None else np.ascontiguousarray(scene["point_bad"], u8).reshape(-1)
+    begin = np.ascontiguousarray(scene["begin"], i32).reshape(-1)
+    ekf = np.ascontiguousarray(scene["edge_kf"], i32).reshape(-1)
+    obs = np.ascontiguousarray(scene["edge_obs"], f32).reshape(-1, 2)
+    w = np.ascontiguousarray(scene["edge_inv_sigma2"], f32).reshape(-1)
+    ecam = np.ascontiguousarray(scene["edge_camera"], i32).reshape(-1)
+    cams = np.ascontiguousarray(scene["cameras"], f32).reshape(-1, 4)
+    K, P, E = len(T), len(pts), len(ekf)
+    if len(fixed) != K or len(begin) != P + 1 or len(obs) != E or len(w) != E or len(ecam) != E or (bad is not None and len(bad) != P):
+        raise ValueError("the arrays of the problem differ in length")
+    c = BaProblemC()
+    c.mode, c.n_iterations, c.n_keyframes, c.n_points, c.n_edges, c.n_cameras = mode, n_iterations, K, P, E, len(cams)
+    c.kf_Tcw, c.kf_fixed, c.points, c.point_bad = T.ctypes.data, fixed.ctypes.data, pts.ctypes.data, None if bad is None else bad.ctypes.data
+    c.point_edge_begin, c.edge_kf, c.edge_obs, c.edge_inv_sigma2 = begin.ctypes.data, ekf.ctypes.data, obs.ctypes.data, w.ctypes.data
+    c.edge_camera, c.cameras = ecam.ctypes.data, cams.ctypes.data
+    out = [np.zeros((max(K, 1), 7)), np.zeros((max(K, 1), 4, 4), f32), np.zeros((max(P, 1), 3)), np.zeros((max(P, 1), 3), f32),
+           np.zeros(max(E, 1), u8), np.zeros(max(E, 1), u8)]
+    r = BaResultC()
+    r.kf_estimate, r.kf_Tcw, r.point_estimate, r.points, r.removed1, r.removed2 = [a.ctypes.data for a in out]
+    arrays = [out[0][:K], out[1][:K], out[2][:P], out[3][:P], out[4][:E], out[5][:E]]
+    return c, r, arrays, (T, fixed, pts, bad, begin, ekf, obs, w, ecam, cams, out)
+
+
+class BundleAdjuster:
+    """Optimizer::LocalBundleAdjustment (src/Optimizer.cc:2147-2405) and Optimizer::BundleAdjustment (:1896-2010) on an ORBmatcher
+    handle, the mapping thread's stream: adjust() runs one problem, every phase a launch of its own and the Levenberg decision on the
+    device.  `_api` exists so that the tests can drive another build through this class."""
+
+    def __init__(self, matcher, max_free=32, max_fixed=64, max_points=8192, max_edges=65536, _api=None):
+        self._api = _api if _api is not None else lib
+        self._matcher = matcher   # the adjuster launches in the handle's stream: keep it alive
+        self._h = ctypes.c_void_p()
+        rc = self._api.uvo_bundle_adjuster_create(matcher._h if matcher is not None else None, max_free, max_fixed, max_points, max_edges, ctypes.byref(self._h))
+        if rc:
+            self._h = None
+            raise UvoError(rc, "uvo_bundle_adjuster_create")
+
+    def close(self):
+        if getattr(self, "_h", None) and self._api is not None:
+            self._api.uvo_bundle_adjuster_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def adjust(self, scene, mode=UVO_BA_LOCAL, n_iterations=0):
+        """scene: the dict ba_marshal() describes -> BaResult."""
+        c, r, arrays, keep = ba_marshal(scene, mode, n_iterations)
+        rc = self._api.uvo_bundle_adjust(self._h, ctypes.byref(c), ctypes.byref(r))
+        if rc:
+            raise UvoError(rc, "uvo_bundle_adjust")
+        return BaResult(r, arrays)
+
+    def trace(self):
+        """Test tap: BaTrace of the last adjust() call."""
+        c = BaTraceC()
+        rc = self._api.uvo_bundle_adjuster_trace(self._h, ctypes.byref(c))
+        if rc:
+            raise UvoError(rc, "uvo_bundle_adjuster_trace")
+        return BaTrace(c)
 
 
 class InitializerResultC(ctypes.Structure):
