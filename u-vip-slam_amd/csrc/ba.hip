@@ -1,13 +1,13 @@
 // Optimizer::LocalBundleAdjustment (src/Optimizer.cc:2147-2405) and Optimizer::BundleAdjustment (:1896-2010) as one call.  All arithmetic,
 // the phases and their launch sequence are ba_core.hpp, shared with the host build tests/emu/ba_emu.cpp; this file is the device's Team
-// -- which lane takes which entry, how the 256 lane sums meet -- one kernel per phase, and the host side of the C ABI.
+// -- which lane takes which entry; how the 256 lane sums meet is lane_team.hpp's LaneTeam -- one kernel per phase, and the host side of
+// the C ABI.
 //
 // A phase is one launch with one workgroup of 256 lanes per block; the launches of a call follow each other in the matcher's stream.
 // No kernel waits for another workgroup: what a phase needs of an earlier one is in global memory when it starts.  The Levenberg
 // decision is taken by k_ba_lin_ctl and k_ba_trial_ctl (one workgroup) and left as a status word, which the host reads through
 // page-locked memory after a stream synchronise to choose the next launches: one read per trial and one per optimize(), at most
-// 2 + 15 x 10 a call in local mode.  A HIP error ends the call at once.  The reduction is poseopt.hip's: a butterfly of __shfl_xor
-// inside each wavefront, one LDS word per wavefront and sum, one barrier, alternating between two buffers.
+// 2 + 15 x 10 a call in local mode.  A HIP error ends the call at once.  The reduction is lane_team.hpp's.
 #include <cstring>
 #include <vector>
 
@@ -18,61 +18,10 @@
 namespace uvo {
 namespace {
 
-struct BaTeam {
-  double* red;    // LDS [2][4][kSchurSums]
-  int32_t* redi;  // LDS [2][4]
-  double* store;  // LDS [kSchurSums]
-  double* v;      // LDS [2][6 * kMaxFree]
-  int phase;
-  __device__ __forceinline__ bool lead() const { return threadIdx.x == 0; }
-  __device__ __forceinline__ double* shared() const { return store; }
+struct BaTeam : LaneTeam<ba::kSchurSums> {
+  double* v;  // LDS [2][6 * kMaxFree]
   __device__ __forceinline__ double* vec() const { return v; }
-  template <int K, class F>
-  __device__ __forceinline__ const double* gather(F f) {
-    double acc[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) acc[k] = 0.;
-    f((int)threadIdx.x, acc);
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1)
-#pragma unroll
-      for (int k = 0; k < K; ++k) acc[k] = acc[k] + __shfl_xor(acc[k], m);
-    double* buf = red + phase * 4 * ba::kSchurSums;
-    phase ^= 1;
-    const int wave = wave_in_block();
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-      for (int k = 0; k < K; ++k) buf[wave * ba::kSchurSums + k] = acc[k];
-    __syncthreads();
-    return buf;
-  }
-  static __device__ __forceinline__ double combine(const double* buf, int k) {
-    return (buf[k] + buf[ba::kSchurSums + k]) + (buf[2 * ba::kSchurSums + k] + buf[3 * ba::kSchurSums + k]);
-  }
-  template <int K, class F>
-  __device__ __forceinline__ void sum(F f, double* out) {
-    const double* buf = gather<K>(f);
-#pragma unroll
-    for (int k = 0; k < K; ++k) out[k] = combine(buf, k);
-  }
-  template <int K, class F>
-  __device__ __forceinline__ void sum_shared(F f, double* out) {
-    const double* buf = gather<K>(f);
-    const int k = (int)threadIdx.x;
-    if (k < K) out[k] = combine(buf, k);
-    __syncthreads();
-  }
-  template <class F>
-  __device__ __forceinline__ int count(F f) {
-    int c = f((int)threadIdx.x);
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m);
-    int32_t* buf = redi + phase * 4;
-    phase ^= 1;
-    if ((threadIdx.x & 63) == 0) buf[wave_in_block()] = c;
-    __syncthreads();
-    return buf[0] + buf[1] + buf[2] + buf[3];
-  }
+  // the maximum over the lanes, through the reduction's words and its barrier
   template <class F>
   __device__ __forceinline__ double maxr(F f) {
     double m = f((int)threadIdx.x);
@@ -108,7 +57,7 @@ struct BaTeam {
     __shared__ double s_store[ba::kSchurSums];                               \
     __shared__ double s_vec[2 * 6 * ba::kMaxFree];                           \
     __shared__ int32_t s_redi[2 * 4];                                        \
-    BaTeam T = {s_red, s_redi, s_store, s_vec, 0};                           \
+    BaTeam T = {{s_red, s_redi, s_store, 0}, s_vec};                         \
     ba::run_phase<ba::kMutNone>(ph, W, T, (int)blockIdx.x);                  \
   }
 

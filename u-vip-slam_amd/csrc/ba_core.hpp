@@ -773,37 +773,11 @@ inline int derive(int K, const uint8_t* fixed, int P, const int32_t* pt_begin, i
   return 0;
 }
 
-// the host's team: one thread that plays lanes 0..255 in turn
+// the host's team: lane_team.hpp's walk of the reduction shape, one thread that plays lanes 0..255 in turn
 #if !defined(__HIP_DEVICE_COMPILE__)
-struct HostTeam {
-  double store[kSchurSums];
+struct HostTeam : HostLaneTeam<kSchurSums> {
   double v[2 * 6 * kMaxFree];
-  bool lead() const { return true; }
-  double* shared() { return store; }
   double* vec() { return v; }
-  template <int K, class F>
-  void sum(F f, double* out) {
-    static thread_local double s[kLanes][K];
-    for (int l = 0; l < kLanes; ++l) {
-      for (int k = 0; k < K; ++k) s[l][k] = 0.;
-      f(l, s[l]);
-    }
-    for (int w = 0; w < kLanes; w += 64)
-      for (int m = 32; m >= 1; m >>= 1)
-        for (int l = 0; l < m; ++l)
-          for (int k = 0; k < K; ++k) s[w + l][k] = s[w + l][k] + s[w + l + m][k];
-    for (int k = 0; k < K; ++k) out[k] = (s[0][k] + s[64][k]) + (s[128][k] + s[192][k]);
-  }
-  template <int K, class F>
-  void sum_shared(F f, double* out) {
-    sum<K>(f, out);
-  }
-  template <class F>
-  int count(F f) {
-    int c = 0;
-    for (int l = 0; l < kLanes; ++l) c += f(l);
-    return c;
-  }
   template <class F>
   double maxr(F f) {
     double m = f(0);

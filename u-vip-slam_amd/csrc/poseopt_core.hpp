@@ -14,8 +14,8 @@
 // The sums of a linearisation go to a place all members read (Team::shared(): 28 words of LDS on the device), so that they do not
 // occupy 56 registers of every lane for the ten trials that use them; a trial's one sum comes back in a register.
 // The shape depends on nothing but the edge index: not on n, not on the values, not on how many edges are active.  A Team does the
-// walking: the device's (poseopt.hip) is the 256 lanes of a workgroup, the host's (HostTeam below) one thread that plays lane 0..255
-// in turn and folds as in 2 and 3.  There are 21 + 6 + 1 sums per linearisation (H's upper triangle, b, the robust chi2) and one
+// walking: the device's (LaneTeam) is the 256 lanes of a workgroup, the host's (HostLaneTeam) one thread that plays lane 0..255
+// in turn and folds as in 2 and 3; both are lane_team.hpp's, which sim3opt and ba walk too.  There are 21 + 6 + 1 sums per linearisation (H's upper triangle, b, the robust chi2) and one
 // per trial (the robust chi2 at the tried pose).  Counts are integers and need no rule.
 //
 // Everything that is not a sum over edges -- the 6 x 6 solve, exp, the pose product, the Levenberg decision -- is computed by every
@@ -35,6 +35,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "lane_team.hpp"
 #include "sim3_core.hpp"
 
 #if defined(__HIPCC__)
@@ -52,7 +53,7 @@
 namespace uvo {
 namespace poseopt {
 
-constexpr int kLanes = 256;
+constexpr int kLanes = kTeamLanes;
 constexpr int kRounds = 4;
 constexpr int kMaxTrials = 10;        // _maxTrialsAfterFailure
 constexpr int kSums = 28;             // 21 of H, 6 of b, the robust chi2
@@ -367,34 +368,7 @@ PO_HD double trial_scale(const double dx[6], double lambda, const double* b) {
 
 // ---- the host's team -----------------------------------------------------------------------------------------------------------------
 #if !defined(__HIP_DEVICE_COMPILE__)
-struct HostTeam {
-  double store[kSums];
-  bool lead() const { return true; }
-  double* shared() { return store; }
-  template <int K, class F>
-  void sum_shared(F f, double* out) {
-    sum<K>(f, out);
-  }
-  template <int K, class F>
-  void sum(F f, double* out) {
-    static thread_local double s[kLanes][K];
-    for (int l = 0; l < kLanes; ++l) {
-      for (int k = 0; k < K; ++k) s[l][k] = 0.;
-      f(l, s[l]);
-    }
-    for (int w = 0; w < kLanes; w += 64)
-      for (int m = 32; m >= 1; m >>= 1)
-        for (int l = 0; l < m; ++l)
-          for (int k = 0; k < K; ++k) s[w + l][k] = s[w + l][k] + s[w + l + m][k];
-    for (int k = 0; k < K; ++k) out[k] = (s[0][k] + s[64][k]) + (s[128][k] + s[192][k]);
-  }
-  template <class F>
-  int count(F f) {
-    int c = 0;
-    for (int l = 0; l < kLanes; ++l) c += f(l);
-    return c;
-  }
-};
+using HostTeam = HostLaneTeam<kSums>;
 #endif
 
 // ---- the call --------------------------------------------------------------------------------------------------------------------------

@@ -431,28 +431,12 @@ PO_HD double trial_scale(const double dx[7], double lambda, const double* b) {
 }
 
 // ---- the host's team -----------------------------------------------------------------------------------------------------------------
-// poseopt::HostTeam's walk of the reduction shape, with this core's 36 shared words and the similarities' 360
+// lane_team.hpp's walk of the reduction shape, with this core's 36 shared words and the similarities' 360
 #if !defined(__HIP_DEVICE_COMPILE__)
-struct HostTeam {
-  poseopt::HostTeam walk;
-  double store[kSums];
+struct HostTeam : HostLaneTeam<kSums> {
   double simw[kSims * kSimWords];
-  bool lead() const { return true; }
   double uni(double v) const { return v; }
-  double* shared() { return store; }
   double* sims() { return simw; }
-  template <int K, class F>
-  void sum_shared(F f, double* out) {
-    walk.template sum<K>(f, out);
-  }
-  template <int K, class F>
-  void sum(F f, double* out) {
-    walk.template sum<K>(f, out);
-  }
-  template <class F>
-  int count(F f) {
-    return walk.count(f);
-  }
   template <class F>
   void each(F f) {
     for (int l = 0; l < kLanes; ++l) f(l);
