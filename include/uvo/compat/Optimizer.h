@@ -16,8 +16,30 @@
 //     + const int nInliers = USLAM::Optimizer::OptimizeSim3(sim3opt, mpCurrentKF, pKF, vpMapPointMatches, gScm, 10);  // a USLAM::Sim3Optimizer
 //
 // and an overload over the list of candidates that issues ONE device call; the caller takes the first candidate in order with
-// nInliers >= 10.  With it the path from loop candidate to accepted loop links nothing of the reference's Optimizer.  The IMU overloads
-// of PoseOptimization (:319, :779), OptimizeEssentialGraph and the NavState bundle adjustments stay with the reference's Optimizer.
+// nInliers >= 10.  With it the path from loop candidate to accepted loop links nothing of the reference's Optimizer.
+// OptimizeEssentialGraph and the NavState bundle adjustments stay with the reference's Optimizer.
+//
+// The two IMU overloads of Optimizer::PoseOptimization (src/Optimizer.cc:779-1103 over a key frame, :319-777 over the last frame) over
+// the C ABI's nav optimizer (uvo_nav_* in uvo/uvo.h), for Tracking::TrackWithIMU (src/Tracking.cc:1099, :1105), TrackLocalMapWithIMU
+// (:1996, :2006) and IMU_Relocalisation (:3035):
+//
+//     - Optimizer::PoseOptimization(&mCurrentFrame, mpLastKeyFrame, imupreint, mpLocalMapper->GetGravityVec(), grot, true, d0, dcov);
+//     + USLAM::Optimizer::PoseOptimization(navopt, navprm, &mCurrentFrame, mpLastKeyFrame, imupreint, mpLocalMapper->GetGravityVec(), grot, true, d0, dcov);
+//
+// navopt: a USLAM::NavOptimizer; navprm: a USLAM::NavParams, what the reference reads from statics (ConfigParam::GetEigTbc(),
+// IMUData::getGyrBiasRW2() / getAccBiasRW2()).  The overload is chosen as the reference's is, by the type of the second argument: one
+// with a member mNavStatePrior is a frame (30 unknowns, its correspondences and its prior enter), any other a key frame (15 unknowns).
+// Needed of the frame type besides PoseOptimization(Frame*)'s members: GetNavState(), SetNavState(ns), mNavStatePrior, mMargCovInv
+// ((i, j) access), mHas_depth, mDepth, mDepth_time, mTimeStamp; of the key frame GetNavState() and mTimeStamp; of NavState Get_P(),
+// Get_V(), Get_R().unit_quaternion() (x(), y(), z(), w()), Get_RotMatrix(), Get_BiasGyr(), Get_BiasAcc(), Get_dBias_Gyr(),
+// Get_dBias_Acc() ((i) access) and Set_Pos, Set_Vel, Set_Rot(SO3), Set_DeltaBiasGyr, Set_DeltaBiasAcc, the SO3 constructible from its
+// quaternion type and that from (w, x, y, z); of the preintegration the getters of uvo_nav_problem's fields ((i), (i, j) access).
+// The reference's effects are kept: mvbOutlier of BOTH frames cleared only where a map point exists and rewritten there; SetNavState
+// with the recovered P, V, R and delta biases; the pose of UpdatePoseFromNS written through pose_data(frame); with bComputeMarg
+// mMargCovInv and mNavStatePrior of the frame.  On the early return (fewer than 3 or 4 correspondences) 0 is returned and nothing but
+// the cleared flags is changed.  The depth edge's information is 1 / cov1^2, cov1 = shi^2 depth_cov^2 + e3^T Rwb^T CovPos Rwb e3 with
+// CovPos the 3 x 3 POSITION block of CovPVPhi: the reference writes block(0,0,2,2) into a 3 x 3 matrix there (:470, :913), which
+// Eigen does not define.  grot is taken and not read, as in the reference.
 //
 // Optimizer::LocalBundleAdjustment(pKF, pbStopFlag, pMap, pLM) (src/Optimizer.cc:2147-2405, called at src/LocalMapping.cc:807) and
 // Optimizer::BundleAdjustment / GlobalBundleAdjustemnt / RecoveryBundleAdjustemnt (:1879-2010, src/Tracking.cc:1480, :1807) over the C
@@ -80,6 +102,32 @@ class PoseOptimizer {
   PoseOptimizer(const PoseOptimizer&);
   PoseOptimizer& operator=(const PoseOptimizer&);
   uvo_pose_optimizer* o_;
+};
+
+// the owner of a nav optimizer set and of the gathering buffers of both frames
+class NavOptimizer {
+ public:
+  NavOptimizer(uvo_klt* klt, int max_points, int max_problems = 1) : o_(0) { uvo_nav_optimizer_create(klt, max_problems, max_points, &o_); }
+  ~NavOptimizer() { uvo_nav_optimizer_destroy(o_); }
+  bool ok() const { return o_ != 0; }
+  uvo_nav_optimizer* handle() { return o_; }
+  struct Gathered {
+    std::vector<float> p3d, p2d, inv_sigma2;
+    std::vector<int32_t> index;
+    std::vector<uint8_t> outlier;
+  };
+  Gathered cur, last;
+
+ private:
+  NavOptimizer(const NavOptimizer&);
+  NavOptimizer& operator=(const NavOptimizer&);
+  uvo_nav_optimizer* o_;
+};
+
+// what the reference's IMU overloads read from statics
+struct NavParams {
+  double Tbc[16];  // ConfigParam::GetEigTbc(), row-major
+  double gyr_bias_rw2, acc_bias_rw2;  // IMUData::getGyrBiasRW2(), getAccBiasRW2()
 };
 
 namespace detail {
@@ -422,6 +470,145 @@ int OptimizeSim3(Sim3Optimizer& opt, KF* pKF1, KF* pKF2, std::vector<MP*>& vpMat
   return inl[0];
 }
 
+
+}  // namespace Optimizer
+
+namespace detail {
+template <class NS>
+void nav_state_of(const NS& ns, uvo_nav_state& s) {
+  for (int i = 0; i < 3; ++i) {
+    s.P[i] = ns.Get_P()(i), s.V[i] = ns.Get_V()(i), s.bg[i] = ns.Get_BiasGyr()(i), s.ba[i] = ns.Get_BiasAcc()(i);
+    s.dbg[i] = ns.Get_dBias_Gyr()(i), s.dba[i] = ns.Get_dBias_Acc()(i);
+  }
+  s.q[0] = ns.Get_R().unit_quaternion().x(), s.q[1] = ns.Get_R().unit_quaternion().y(), s.q[2] = ns.Get_R().unit_quaternion().z();
+  s.q[3] = ns.Get_R().unit_quaternion().w();
+}
+// ns_recov: P, V, R and the delta biases of the result; the biases stay
+template <class NS>
+void nav_state_to(const uvo_nav_state& s, NS& ns) {
+  typedef typename std::decay<decltype(ns.Get_P())>::type Vec;
+  typedef typename std::decay<decltype(ns.Get_R())>::type Rot;
+  typedef typename std::decay<decltype(ns.Get_R().unit_quaternion())>::type Quat;
+  Vec P = ns.Get_P(), V = ns.Get_V(), dbg = ns.Get_dBias_Gyr(), dba = ns.Get_dBias_Acc();
+  for (int i = 0; i < 3; ++i) P(i) = s.P[i], V(i) = s.V[i], dbg(i) = s.dbg[i], dba(i) = s.dba[i];
+  ns.Set_Pos(P), ns.Set_Vel(V), ns.Set_DeltaBiasGyr(dbg), ns.Set_DeltaBiasAcc(dba);
+  ns.Set_Rot(Rot(Quat(s.q[3], s.q[0], s.q[1], s.q[2])));
+}
+template <class M>
+void mat3_of(const M& m, double* o) {
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) o[i * 3 + j] = m(i, j);
+}
+template <class V>
+void vec3_of(const V& v, double* o) {
+  for (int i = 0; i < 3; ++i) o[i] = v(i);
+}
+// the walk of :937-991 and :518-624 over one frame: mvbOutlier cleared where a map point exists, and only there
+template <class Frame>
+void gather_nav(NavOptimizer::Gathered& g, Frame* pFrame) {
+  static_assert(sizeof(pFrame->mvKeysUn[0]) == sizeof(uvo_keypoint), "keypoint layout must be cv::KeyPoint");
+  g.p3d.clear(), g.p2d.clear(), g.inv_sigma2.clear(), g.index.clear();
+  const int N = (int)pFrame->mvpMapPoints.size();
+  for (int i = 0; i < N; i++) {
+    if (!pFrame->mvpMapPoints[i]) continue;
+    float X[3];
+    world_pos(pFrame->mvpMapPoints[i]->GetWorldPos(), X);
+    g.p3d.insert(g.p3d.end(), X, X + 3);
+    pFrame->mvbOutlier[i] = false;
+    const uvo_keypoint& kp = reinterpret_cast<const uvo_keypoint&>(pFrame->mvKeysUn[i]);
+    g.p2d.push_back(kp.x), g.p2d.push_back(kp.y);
+    g.inv_sigma2.push_back(pFrame->mvInvLevelSigma2[kp.octave]);
+    g.index.push_back((int32_t)i);
+  }
+  g.outlier.assign(g.index.empty() ? 1 : g.index.size(), 0);
+}
+// the frame form's part: the last frame's correspondences, its prior and its information
+template <class L>
+auto nav_last(NavOptimizer& opt, L* pLast, uvo_nav_problem& p, uvo_nav_result& r, int) -> decltype((void)pLast->mNavStatePrior, void()) {
+  p.form = UVO_NAV_FRAME;
+  gather_nav(opt.last, pLast);
+  const int n = (int)opt.last.index.size();
+  p.n_last = n;
+  if (n) p.p3d_last = &opt.last.p3d[0], p.p2d_last = &opt.last.p2d[0], p.inv_sigma2_last = &opt.last.inv_sigma2[0];
+  r.outlier_last = &opt.last.outlier[0], r.outlier_last_cap = (int32_t)opt.last.outlier.size();
+  nav_state_of(pLast->mNavStatePrior, p.prior);
+  for (int i = 0; i < 15; ++i)
+    for (int j = 0; j < 15; ++j) p.prior_info[i * 15 + j] = pLast->mMargCovInv(i, j);
+}
+template <class L>
+void nav_last(NavOptimizer&, L*, uvo_nav_problem& p, uvo_nav_result&, long) {
+  p.form = UVO_NAV_KEYFRAME;
+}
+template <class L>
+auto nav_scatter_last(NavOptimizer& opt, L* pLast, int) -> decltype((void)pLast->mNavStatePrior, void()) {
+  for (size_t j = 0; j < opt.last.index.size(); ++j) pLast->mvbOutlier[opt.last.index[j]] = opt.last.outlier[j] != 0;
+}
+template <class L>
+void nav_scatter_last(NavOptimizer&, L*, long) {}
+}  // namespace detail
+
+namespace Optimizer {
+
+// int Optimizer::PoseOptimization(FrameKTL* pFrame, KeyFrame* pLastKF, const IMUPreintegrator&, const cv::Mat& gw, const cv::Mat& grot,
+// const bool& bComputeMarg, double ini_depth, double depth_cov) and the overload over FrameKTL* pLastFrame.  Returns
+// nInitialCorrespondences - nBad, 0 on the early return, or -1 when the library call fails (the frames are then as the gathering left
+// them).
+template <class Frame, class Last, class Pre, class Mat>
+int PoseOptimization(NavOptimizer& opt, const NavParams& prm, Frame* pFrame, Last* pLast, const Pre& imupreint, const Mat& gw, const Mat& grot,
+                     const bool& bComputeMarg, double ini_depth, double depth_cov) {
+  (void)grot;
+  if (!opt.ok()) return -1;
+  uvo_nav_problem p = uvo_nav_problem();
+  uvo_nav_result r = uvo_nav_result();
+  detail::gather_nav(opt.cur, pFrame);
+  detail::nav_last(opt, pLast, p, r, 0);
+  const int n = (int)opt.cur.index.size();
+  p.n = n;
+  if (n) p.p3d = &opt.cur.p3d[0], p.p2d = &opt.cur.p2d[0], p.inv_sigma2 = &opt.cur.inv_sigma2[0];
+  r.outlier = &opt.cur.outlier[0], r.outlier_cap = (int32_t)opt.cur.outlier.size();
+  p.has_depth = pFrame->mHas_depth ? 1 : 0, p.compute_marg = bComputeMarg ? 1 : 0;
+  detail::nav_state_of(pFrame->GetNavState(), p.cur);
+  detail::nav_state_of(pLast->GetNavState(), p.last);
+  p.dT = imupreint.getDeltaTime();
+  detail::vec3_of(imupreint.getDeltaP(), p.dP), detail::vec3_of(imupreint.getDeltaV(), p.dV), detail::mat3_of(imupreint.getDeltaR(), p.dR);
+  detail::mat3_of(imupreint.getJPBiasg(), p.JPg), detail::mat3_of(imupreint.getJPBiasa(), p.JPa), detail::mat3_of(imupreint.getJVBiasg(), p.JVg);
+  detail::mat3_of(imupreint.getJVBiasa(), p.JVa), detail::mat3_of(imupreint.getJRBiasg(), p.JRg);
+  for (int i = 0; i < 9; ++i)
+    for (int j = 0; j < 9; ++j) p.cov_pvphi[i * 9 + j] = imupreint.getCovPVPhi()(i, j);
+  float g[3];
+  detail::world_pos(gw, g);
+  for (int i = 0; i < 3; ++i) {
+    p.gw[i] = g[i], p.Pbc[i] = prm.Tbc[i * 4 + 3];
+    for (int j = 0; j < 3; ++j) p.Rbc[i * 3 + j] = prm.Tbc[i * 4 + j];
+  }
+  p.fx = pFrame->fx, p.fy = pFrame->fy, p.cx = pFrame->cx, p.cy = pFrame->cy;
+  p.gyr_bias_rw2 = prm.gyr_bias_rw2, p.acc_bias_rw2 = prm.acc_bias_rw2;
+  if (p.has_depth) {
+    p.shi = (pFrame->mTimeStamp - pLast->mTimeStamp) / (pFrame->mDepth_time - pLast->mTimeStamp);
+    p.depth_meas = pFrame->mDepth - ini_depth;
+    double R[9], cov3 = 0.;
+    detail::mat3_of(pLast->GetNavState().Get_RotMatrix(), R);
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) cov3 = cov3 + (R[i * 3 + 2] * p.cov_pvphi[i * 9 + j]) * R[j * 3 + 2];  // the 3 x 3 position block
+    const double cov1 = (p.shi * p.shi * depth_cov * depth_cov) + cov3;
+    p.depth_info = 1 / (cov1 * cov1);
+  }
+  if (uvo_nav_optimize(opt.handle(), &p, 1, &r) != UVO_OK) return -1;
+  if (r.rounds == 0) return 0;
+  for (int j = 0; j < n; ++j) pFrame->mvbOutlier[opt.cur.index[j]] = opt.cur.outlier[j] != 0;
+  detail::nav_scatter_last(opt, pLast, 0);
+  typename std::decay<decltype(pFrame->GetNavState())>::type ns = pFrame->GetNavState();
+  detail::nav_state_to(r.ns, ns);
+  pFrame->SetNavState(ns);
+  float* T = pose_data(*pFrame);
+  for (int e = 0; e < 16; ++e) T[e] = r.Tcw[e];
+  if (bComputeMarg) {
+    for (int i = 0; i < 15; ++i)
+      for (int j = 0; j < 15; ++j) pFrame->mMargCovInv(i, j) = r.marg_cov_inv[i * 15 + j];
+    pFrame->mNavStatePrior = ns;
+  }
+  return r.n_inliers;
+}
 
 // int Optimizer::PoseOptimization(Frame* pFrame).  Returns nInitialCorrespondences - nBad, or -1 when the library call fails (the
 // frame is then as the gathering left it: mvbOutlier cleared for the indices with a map point, the pose untouched).

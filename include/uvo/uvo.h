@@ -1111,6 +1111,106 @@ int uvo_pose_optimize(uvo_pose_optimizer* o, const uvo_pose_problem* problems, i
 int uvo_pose_optimizer_trace(uvo_pose_optimizer* o, int problem, uvo_pose_trace* out);
 
 /* ------------------------------------------------------------------------------------------------
+ * Visual-inertial pose optimisation -- replaces the two IMU overloads of Optimizer::PoseOptimization and the parts of g2o,
+ * src/IMU/g2otypes.cpp, NavState.cpp and so3.cpp they run, as TrackWithIMU (src/Tracking.cc:1099,1105), TrackLocalMapWithIMU
+ * (:1996,2006) and IMU_Relocalisation (:3035) call them:
+ *   UVO_NAV_KEYFRAME  (FrameKTL*, KeyFrame*, IMUPreintegrator, ...), src/Optimizer.cc:779-1103: 15 unknowns (the frame's P, V, R and
+ *                     its delta biases), the last key frame fixed; edges: IMU, bias, depth (has_depth), one per correspondence.
+ *   UVO_NAV_FRAME     (FrameKTL*, FrameKTL*, IMUPreintegrator, ...), :319-777: 30 unknowns, the last frame free and tied by the prior
+ *                     edge (mNavStatePrior, mMargCovInv); the correspondences of both frames.
+ * Four rounds of optimize(10), threshold 5.991 in each, THE ESTIMATES RESET TO THE INPUT AT THE START OF EVERY ROUND, both frames'
+ * edges classified after each (const float chi2: the comparison is made in float; a NaN chi2 is an inlier), the Huber kernel taken
+ * off the reprojection edges only after round index 2, and the break test on the number of ALL edges of the graph (n + n_last + 2 + the
+ * prior + the depth edge < 10: one round).  n < 3 (key-frame form) or n < 4 (frame form): 0 inliers, 0 rounds, the state as it came.
+ * Hessian order: frame PVR, frame bias, last PVR, last bias.  ONE call optimises a list of problems: one upload, one launch (one
+ * workgroup per problem, all four rounds), one download, nothing allocated.  With compute_marg the result carries the current frame's
+ * 15 x 15 block of inv(H) -- H as the LAST linearisation of the last round run left it, not a new one at the final estimate -- and
+ * mMargCovInv as the overload stores it: the inverses of the 9 x 9 and the 6 x 6 diagonal blocks, the rest zero (key-frame form,
+ * :1083-1085), or the inverse of the whole 15 x 15 (frame form, :752-757).
+ * Semantics are pinned to the reference's sources by tests/navopt_model.py.  Departures (contract 12):
+ *   - sums over the correspondences are reduced in a fixed tree over 256 lanes; the single edges are added in one stated order;
+ *   - every solve and inverse (H + lambda I, CovPVPhi, the marginals, mMargCovInv) is one dense unpivoted LDL^T that fails unless
+ *     every pivot is finite and > 0, where the reference has Cholmod and Eigen's inverse();
+ *   - sin, cos and atan are the library's own; SO3's normalisation on every copy is done once where a quaternion is made;
+ *   - the frame form's spinv.block(0,1), which computeMarginals never fills, is read as the joint 15 x 15 block it means;
+ *   - the depth edge's information is the caller's scalar: the reference assigns a 2 x 2 block to a 3 x 3 matrix (:470, :913).
+ * ---------------------------------------------------------------------------------------------- */
+#define UVO_NAV_KEYFRAME 0
+#define UVO_NAV_FRAME 1
+typedef struct uvo_nav_optimizer uvo_nav_optimizer;
+
+typedef struct uvo_nav_state {   /* NavState */
+  double P[3], V[3];
+  double q[4];             /* R as SO3 holds it: a unit quaternion x y z w */
+  double bg[3], ba[3];     /* BiasGyr, BiasAcc */
+  double dbg[3], dba[3];   /* dBias_g, dBias_a */
+} uvo_nav_state;
+
+typedef struct uvo_nav_problem {
+  int32_t form;            /* UVO_NAV_KEYFRAME or UVO_NAV_FRAME */
+  int32_t has_depth;       /* pFrame->mHas_depth */
+  int32_t compute_marg;    /* bComputeMarg */
+  int32_t n, n_last;       /* correspondences of the current and (frame form) the last frame: 0..max_points each */
+  int32_t pad_;
+  uvo_nav_state cur, last; /* GetNavState() of the frame and of the last frame or key frame */
+  double dT, dP[3], dV[3], dR[9];                    /* getDeltaTime, getDeltaP, getDeltaV, getDeltaR (row-major) */
+  double JPg[9], JPa[9], JVg[9], JVa[9], JRg[9];     /* getJPBiasg, getJPBiasa, getJVBiasg, getJVBiasa, getJRBiasg */
+  double cov_pvphi[81];    /* getCovPVPhi(), inverted in the library */
+  double gw[3], Rbc[9], Pbc[3];
+  double fx, fy, cx, cy;
+  double gyr_bias_rw2, acc_bias_rw2;                 /* IMUData::getGyrBiasRW2(), getAccBiasRW2() */
+  uvo_nav_state prior;     /* frame form: the last frame's mNavStatePrior */
+  double prior_info[225];  /* frame form: the last frame's mMargCovInv, row-major */
+  double depth_meas;       /* mDepth - ini_depth */
+  double shi;              /* (mTimeStamp - last mTimeStamp) / (mDepth_time - last mTimeStamp) */
+  double depth_info;       /* the depth edge's information */
+  const float* p3d;        /* [n][3], [n][2], [n]: as uvo_pose_problem */
+  const float* p2d;
+  const float* inv_sigma2;
+  const float* p3d_last;   /* [n_last]...: the last frame's, frame form only */
+  const float* p2d_last;
+  const float* inv_sigma2_last;
+} uvo_nav_problem;
+
+typedef struct uvo_nav_result {
+  uvo_nav_state ns;        /* ns_recov: SetNavState */
+  float Tcw[16];           /* UpdatePoseFromNS */
+  int32_t n_inliers;       /* nInitialCorrespondences - nBad */
+  int32_t rounds;          /* 0 (too few correspondences), 1 (fewer than 10 edges) or 4 */
+  int32_t marg_ok;         /* compute_marg: every factorisation behind the marginals succeeded */
+  int32_t outlier_cap, outlier_last_cap;  /* UVO_E_CAPACITY when smaller than n, n_last */
+  int32_t pad_;
+  uint8_t* outlier;        /* caller's [n]: mvbOutlier of the current frame's correspondences; may be NULL */
+  uint8_t* outlier_last;   /* caller's [n_last]: the last frame's (frame form); may be NULL */
+  double marg_cov[225];    /* the current frame's (PVR, bias) block of inv(H), row-major; zero without compute_marg */
+  double marg_cov_inv[225];/* mMargCovInv */
+} uvo_nav_result;
+
+/* test tap: what the Levenberg driver saw */
+typedef struct uvo_nav_trace_lin {
+  int32_t round, iteration;
+  double H[465];           /* upper triangle of the 15 x 15 or 30 x 30 matrix, row-major, packed, before lambda; zero beyond */
+  double b[30];
+  double chi2;
+} uvo_nav_trace_lin;
+typedef struct uvo_nav_trace {
+  int32_t n_lin, n_trials;
+  uvo_nav_trace_lin lin[40];
+  uvo_pose_trace_trial trial[400];
+} uvo_nav_trace;
+
+/* max_problems 1..64, max_points 1..16384 per frame (UVO_E_BADARG otherwise).  The set launches in the KLT handle's stream and must
+ * be destroyed before it. */
+int uvo_nav_optimizer_create(uvo_klt* k, int max_problems, int max_points, uvo_nav_optimizer** out);
+void uvo_nav_optimizer_destroy(uvo_nav_optimizer* o);
+/* results[j] answers problems[j].  UVO_E_CAPACITY: n_problems > max_problems, an n or n_last > max_points, an outlier mask shorter than
+ * its count.  UVO_E_BADARG: null pointers, negative counts, a form that is neither.  Nothing is written on an error.  n_problems == 0
+ * is a no-op. */
+int uvo_nav_optimize(uvo_nav_optimizer* o, const uvo_nav_problem* problems, int n_problems, uvo_nav_result* results);
+/* test tap: the trace of problem `problem` of the set's last call (UVO_E_BADARG when the last call had no such problem). */
+int uvo_nav_optimizer_trace(uvo_nav_optimizer* o, int problem, uvo_nav_trace* out);
+
+/* ------------------------------------------------------------------------------------------------
  * Sim3Solver -- replaces USLAM::Sim3Solver (include/Sim3Solver.h, src/Sim3Solver.cc) as LoopClosing::ComputeSim3 uses it
  * (src/LoopClosing.cc:373-479): one solver per loop candidate, SetRansacParameters(0.99,2,300), then iterate(5,...) over the candidates
  * in turn until one returns a similarity, whose R, t, s go to SearchBySim3 (uvo_sim3_relative, uvo_search_by_sim3 on the same handle).

@@ -46,6 +46,7 @@ ABI_SYMBOLS = [
     "uvo_glibc_srand", "uvo_glibc_rand_next", "uvo_pnpsolver_set_create", "uvo_pnpsolver_set_destroy", "uvo_pnpsolver_set_clear", "uvo_pnpsolver_add",
     "uvo_pnpsolver_query", "uvo_pnpsolver_iterate", "uvo_pnpsolver_hypotheses",
     "uvo_pose_optimizer_create", "uvo_pose_optimizer_destroy", "uvo_pose_optimize", "uvo_pose_optimizer_trace",
+    "uvo_nav_optimizer_create", "uvo_nav_optimizer_destroy", "uvo_nav_optimize", "uvo_nav_optimizer_trace",
     "uvo_sim3solver_set_create", "uvo_sim3solver_set_destroy", "uvo_sim3solver_set_clear", "uvo_sim3solver_add", "uvo_sim3solver_set_ransac_parameters",
     "uvo_sim3solver_query", "uvo_sim3solver_iterate", "uvo_sim3solver_find", "uvo_sim3solver_hypotheses",
     "uvo_sim3_optimizer_create", "uvo_sim3_optimizer_destroy", "uvo_sim3_optimize", "uvo_sim3_optimizer_trace",
@@ -287,6 +288,11 @@ def _load():
     lib.uvo_pose_optimizer_destroy.restype = None
     lib.uvo_pose_optimize.argtypes = [vp, vp, ci, vp]
     lib.uvo_pose_optimizer_trace.argtypes = [vp, ci, vp]
+    lib.uvo_nav_optimizer_create.argtypes = [vp, ci, ci, vp]
+    lib.uvo_nav_optimizer_destroy.argtypes = [vp]
+    lib.uvo_nav_optimizer_destroy.restype = None
+    lib.uvo_nav_optimize.argtypes = [vp, vp, ci, vp]
+    lib.uvo_nav_optimizer_trace.argtypes = [vp, ci, vp]
     lib.uvo_sim3_optimizer_create.argtypes = [vp, ci, ci, vp]
     lib.uvo_sim3_optimizer_destroy.argtypes = [vp]
     lib.uvo_sim3_optimizer_destroy.restype = None
@@ -1578,6 +1584,149 @@ class PoseOptimizer:
         if rc:
             raise UvoError(rc, "uvo_pose_optimizer_trace")
         return PoseTrace(c)
+
+
+class NavStateC(ctypes.Structure):
+    """uvo_nav_state: P, V, q (x y z w), bg, ba, dbg, dba."""
+    _fields_ = [("P", ctypes.c_double * 3), ("V", ctypes.c_double * 3), ("q", ctypes.c_double * 4), ("bg", ctypes.c_double * 3), ("ba", ctypes.c_double * 3),
+                ("dbg", ctypes.c_double * 3), ("dba", ctypes.c_double * 3)]
+
+    def set(self, s):
+        """s: a dict of arrays under the field names."""
+        for k, _ in self._fields_:
+            getattr(self, k)[:] = [float(v) for v in np.asarray(s[k], np.float64).reshape(-1)]
+        return self
+
+    def get(self):
+        return {k: np.array(getattr(self, k), np.float64) for k, _ in self._fields_}
+
+
+_D = ctypes.c_double
+
+
+class NavProblemC(ctypes.Structure):
+    """uvo_nav_problem."""
+    _fields_ = [("form", ctypes.c_int32), ("has_depth", ctypes.c_int32), ("compute_marg", ctypes.c_int32), ("n", ctypes.c_int32), ("n_last", ctypes.c_int32),
+                ("pad_", ctypes.c_int32), ("cur", NavStateC), ("last", NavStateC), ("dT", _D), ("dP", _D * 3), ("dV", _D * 3), ("dR", _D * 9), ("JPg", _D * 9),
+                ("JPa", _D * 9), ("JVg", _D * 9), ("JVa", _D * 9), ("JRg", _D * 9), ("cov_pvphi", _D * 81), ("gw", _D * 3), ("Rbc", _D * 9), ("Pbc", _D * 3),
+                ("fx", _D), ("fy", _D), ("cx", _D), ("cy", _D), ("gyr_bias_rw2", _D), ("acc_bias_rw2", _D), ("prior", NavStateC), ("prior_info", _D * 225),
+                ("depth_meas", _D), ("shi", _D), ("depth_info", _D), ("p3d", ctypes.c_void_p), ("p2d", ctypes.c_void_p), ("inv_sigma2", ctypes.c_void_p),
+                ("p3d_last", ctypes.c_void_p), ("p2d_last", ctypes.c_void_p), ("inv_sigma2_last", ctypes.c_void_p)]
+
+
+class NavResultC(ctypes.Structure):
+    """uvo_nav_result."""
+    _fields_ = [("ns", NavStateC), ("Tcw", ctypes.c_float * 16), ("n_inliers", ctypes.c_int32), ("rounds", ctypes.c_int32), ("marg_ok", ctypes.c_int32),
+                ("outlier_cap", ctypes.c_int32), ("outlier_last_cap", ctypes.c_int32), ("pad_", ctypes.c_int32), ("outlier", ctypes.c_void_p),
+                ("outlier_last", ctypes.c_void_p), ("marg_cov", _D * 225), ("marg_cov_inv", _D * 225)]
+
+
+class NavTraceLin(ctypes.Structure):
+    """uvo_nav_trace_lin."""
+    _fields_ = [("round", ctypes.c_int32), ("iteration", ctypes.c_int32), ("H", _D * 465), ("b", _D * 30), ("chi2", _D)]
+
+
+class NavTraceC(ctypes.Structure):
+    """uvo_nav_trace."""
+    _fields_ = [("n_lin", ctypes.c_int32), ("n_trials", ctypes.c_int32), ("lin", NavTraceLin * 40), ("trial", PoseTraceTrial * 400)]
+
+
+NAV_KEYFRAME, NAV_FRAME = 0, 1
+NAV_LIN_DTYPE = np.dtype([("round", "<i4"), ("iteration", "<i4"), ("H", "<f8", 465), ("b", "<f8", 30), ("chi2", "<f8")])
+
+
+class NavTrace:
+    """The test tap of one problem: lin (NAV_LIN_DTYPE, one record per linearisation; H the packed upper triangle of the 15 x 15 or
+    30 x 30 matrix), trial (POSE_TRIAL_DTYPE, one per Levenberg trial)."""
+
+    def __init__(self, c):
+        self.lin = np.frombuffer(bytes(c.lin), NAV_LIN_DTYPE)[:c.n_lin].copy()
+        self.trial = np.frombuffer(bytes(c.trial), POSE_TRIAL_DTYPE)[:c.n_trials].copy()
+
+
+class NavResult:
+    """One optimised problem: ns (the recovered NavState, a dict of arrays), Tcw float32[4, 4] by UpdatePoseFromNS, n_inliers, rounds,
+    outlier uint8[n], outlier_last uint8[n_last], marg_cov and marg_cov_inv float64[15, 15], marg_ok."""
+
+    def __init__(self, c, outlier, outlier_last):
+        self.ns = c.ns.get()
+        self.Tcw = np.array(c.Tcw, np.float32).reshape(4, 4)
+        self.n_inliers, self.rounds, self.marg_ok, self.outlier, self.outlier_last = c.n_inliers, c.rounds, c.marg_ok, outlier, outlier_last
+        self.marg_cov, self.marg_cov_inv = np.array(c.marg_cov, np.float64).reshape(15, 15), np.array(c.marg_cov_inv, np.float64).reshape(15, 15)
+
+
+class NavOptimizer:
+    """The two IMU overloads of Optimizer::PoseOptimization (src/Optimizer.cc:319-777 the frame form, :779-1103 the key-frame form) on a
+    KLT handle: optimize() takes a list of independent problems and runs them as one device call."""
+
+    def __init__(self, klt, max_problems=1, max_points=4096, _api=None):
+        self._api = _api if _api is not None else lib
+        self._klt = klt   # the set launches in the handle's stream: keep it alive
+        self._h = ctypes.c_void_p()
+        self.max_problems, self.max_points = max_problems, max_points
+        rc = self._api.uvo_nav_optimizer_create(klt._h if klt is not None else None, max_problems, max_points, ctypes.byref(self._h))
+        if rc:
+            self._h = None
+            raise UvoError(rc, "uvo_nav_optimizer_create")
+
+    def close(self):
+        if getattr(self, "_h", None) and self._api is not None:
+            self._api.uvo_nav_optimizer_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    @staticmethod
+    def problem(sc, keep):
+        """A NavProblemC of a problem given as a dict: form, has_depth, compute_marg, cur, last, prior (dicts of P V q bg ba dbg dba), dT, dP,
+        dV, dR, JPg, JPa, JVg, JVa, JRg, cov, gw, Rbc, Pbc, K = (fx, fy, cx, cy), gyr_rw2, acc_rw2, prior_info, depth_meas, shi, depth_info,
+        edges [n, 6] and edges_last [n_last, 6] (point, observation, invSigma2).  keep: a list that takes the arrays the record points into."""
+        c = NavProblemC()
+        c.form, c.has_depth, c.compute_marg = int(sc["form"]), int(bool(sc["has_depth"])), int(bool(sc["compute_marg"]))
+        c.cur.set(sc["cur"]), c.last.set(sc["last"]), c.prior.set(sc["prior"])
+        for k, name in (("dP", "dP"), ("dV", "dV"), ("dR", "dR"), ("JPg", "JPg"), ("JPa", "JPa"), ("JVg", "JVg"), ("JVa", "JVa"), ("JRg", "JRg"), ("cov", "cov_pvphi"),
+                        ("gw", "gw"), ("Rbc", "Rbc"), ("Pbc", "Pbc"), ("prior_info", "prior_info")):
+            getattr(c, name)[:] = [float(v) for v in np.asarray(sc[k], np.float64).reshape(-1)]
+        c.dT, c.gyr_bias_rw2, c.acc_bias_rw2 = float(sc["dT"]), float(sc["gyr_rw2"]), float(sc["acc_rw2"])
+        c.fx, c.fy, c.cx, c.cy = [float(v) for v in sc["K"]]
+        c.depth_meas, c.shi, c.depth_info = float(sc["depth_meas"]), float(sc["shi"]), float(sc["depth_info"])
+        for key, names in (("edges", ("p3d", "p2d", "inv_sigma2")), ("edges_last", ("p3d_last", "p2d_last", "inv_sigma2_last"))):
+            e = np.asarray(sc.get(key, np.zeros((0, 6))), np.float32).reshape(-1, 6)
+            parts = [np.ascontiguousarray(e[:, :3]), np.ascontiguousarray(e[:, 3:5]), np.ascontiguousarray(e[:, 5])]
+            keep.append(parts)
+            for nm, a in zip(names, parts):
+                setattr(c, nm, a.ctypes.data if len(e) else None)
+            if key == "edges":
+                c.n = len(e)
+            else:
+                c.n_last = len(e)
+        return c
+
+    def optimize(self, problems, outlier_cap=None):
+        """problems: a list of dicts (see problem()) -> a list of NavResult.  outlier_cap (for the tests): the capacity passed for every
+        mask instead of its count."""
+        cp = (NavProblemC * max(len(problems), 1))()
+        cr = (NavResultC * max(len(problems), 1))()
+        keep, masks = [], []
+        for j, sc in enumerate(problems):
+            cp[j] = self.problem(sc, keep)
+            m, ml = np.zeros(max(cp[j].n, 1), np.uint8), np.zeros(max(cp[j].n_last, 1), np.uint8)
+            masks.append((m, ml))
+            cr[j].outlier, cr[j].outlier_last = m.ctypes.data, ml.ctypes.data
+            cr[j].outlier_cap = cp[j].n if outlier_cap is None else outlier_cap
+            cr[j].outlier_last_cap = cp[j].n_last if outlier_cap is None else outlier_cap
+        rc = self._api.uvo_nav_optimize(self._h, cp, len(problems), cr)
+        if rc:
+            raise UvoError(rc, "uvo_nav_optimize")
+        return [NavResult(cr[j], masks[j][0][:cp[j].n].copy(), masks[j][1][:cp[j].n_last if cp[j].form == NAV_FRAME else 0].copy()) for j in range(len(problems))]
+
+    def trace(self, problem=0):
+        """Test tap: NavTrace of problem `problem` of the last optimize() call."""
+        c = NavTraceC()
+        rc = self._api.uvo_nav_optimizer_trace(self._h, problem, ctypes.byref(c))
+        if rc:
+            raise UvoError(rc, "uvo_nav_optimizer_trace")
+        return NavTrace(c)
 
 
 class Sim3SolverParams(ctypes.Structure):
