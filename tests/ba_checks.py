@@ -18,12 +18,12 @@ the tolerance is that spread times MARGIN.  Scenes whose model decisions differ 
 changes) are reported as `unclear` and are held to layers 1 to 4 only."""
 import ctypes
 import os
-import subprocess
 import sys
 
 import numpy as np
 
 import ba_model as bm
+import host_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EPS = 2.0 ** -53
@@ -90,14 +90,8 @@ class Emu:
         assert mutation is None or mutation in MUTATIONS
         self.uvo = uvo
         if mutation not in Emu._libs:
-            src = os.path.join(ROOT, "tests", "emu", "ba_emu.cpp")
-            lib = os.path.join(ROOT, "tests", "emu", "libba_emu%s.so" % ("" if mutation is None else "_" + mutation.lower()))
-            deps = [src, os.path.join(ROOT, "include", "uvo", "uvo.h")] + [os.path.join(ROOT, "u-vip-slam_amd", "csrc", h) for h in
-                                                                           ("epnp_core.hpp", "pnpsolver_core.hpp", "sim3_core.hpp", "poseopt_core.hpp", "ba_core.hpp")]
-            if not os.path.exists(lib) or max(os.path.getmtime(d) for d in deps) > os.path.getmtime(lib):
-                subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off"] +
-                                      (["-DBA_MUT=%d" % MUTATIONS[mutation]] if mutation else []) + ["-o", lib, src])
-            L = ctypes.CDLL(lib)
+            variant = (["-DBA_MUT=%d" % MUTATIONS[mutation]], "_" + mutation.lower()) if mutation else ()
+            L = ctypes.CDLL(host_build.build("ba_emu", *variant))
             vp = ctypes.c_void_p
             L.emu_ba_adjust.argtypes = [vp, vp, vp]
             L.emu_ba_one_trial.argtypes = [vp, vp, vp, vp, ctypes.c_double] + [vp] * 13

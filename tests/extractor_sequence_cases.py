@@ -14,10 +14,10 @@ The handle of every scenario is 320 x 256 (`MAX_W`, `MAX_H`); the walks use thre
 """
 import collections
 import ctypes
-import os
 
 import numpy as np
 
+import host_build
 import oracle_lib
 
 KP = oracle_lib.KP
@@ -94,7 +94,7 @@ def geom_probe(cfg, w, h):
     column table, row table, quad-tree path tables), -5 = UVO_E_UNSUPPORTED."""
     global _geom
     if _geom is None:
-        _geom = ctypes.CDLL(os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu", "libgeom_emu.so"))
+        _geom = ctypes.CDLL(host_build.build("geom_emu"))
         _geom.emu_geom_probe.argtypes = [ctypes.c_int, ctypes.c_float] + [ctypes.c_int] * 7 + [ctypes.c_void_p] * 2
     wh, ok = np.zeros(2 * cfg.nlevels, np.int32), np.zeros(cfg.nlevels, np.int32)
     rc = _geom.emu_geom_probe(cfg.nfeatures, cfg.scale, cfg.nlevels, MAX_W, MAX_H, cfg.max_batch, cfg.max_input_keypoints, w, h, wh.ctypes.data, ok.ctypes.data)
@@ -106,7 +106,7 @@ def default_tile_plan_on_host(oracle, cfg, img, max_lds=160 * 1024):
     tiles_for(level-1 width, 34) x tiles_for(level-1 height, 27) tiles), executed on the host by tests/emu/pyr_tiles_emu.cpp, which holds
     every load and store of the plan to the planes and the LDS allocation.  -> (the emulation's verdict: 0 = every property holds,
     2 = a level outside the 12-byte window (no plan: per-level launches), 3 = no plan within the LDS; planes equal the oracle's)"""
-    emu = ctypes.CDLL(os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu", "libpyr_tiles_emu.so"))
+    emu = ctypes.CDLL(host_build.build("pyr_tiles_emu"))
     vp, ci = ctypes.c_void_p, ctypes.c_int
     emu.emu_pyr_tiles_run.argtypes = [vp, ci, ci, vp, vp, ci, ci, vp, vp, vp, ctypes.c_uint32, vp, vp, vp, vp]
     oe = oracle.extractor(cfg.nfeatures, cfg.scale, cfg.nlevels, cfg.fast_th)

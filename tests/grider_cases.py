@@ -98,20 +98,8 @@ def handle_capacities(max_batch=HANDLE_CFG[3]):
     """(pixels, ROIs, ROIs x quota) that uvo_grider_fast accepts on the test's handle, from csrc/extractor_geom.cpp run on the host
     (tests/emu/grider_geom_emu.cpp)."""
     import ctypes
-    import importlib.util
-    import os
-    import subprocess
-    here = os.path.dirname(os.path.abspath(__file__))
-    root = os.path.dirname(here)
-    so = os.path.join(here, "emu", "libgrider_geom_emu.so")
-    srcs = [os.path.join(here, "emu", "grider_geom_emu.cpp"), os.path.join(here, "emu", "geom_emu.cpp"),
-            os.path.join(root, "u-vip-slam_amd", "csrc", "extractor_geom.cpp")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(f) for f in srcs):   # built on first use, as build() does it
-        spec = importlib.util.spec_from_file_location("uvo_build", os.path.join(root, "u-vip-slam_amd", "build.py"))
-        build = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(build)
-        subprocess.check_call([build.HIPCC, "-O2", "-std=c++17", "-fPIC", "-shared", "-x", "hip", "--offload-arch=gfx950", "-o", so, srcs[0]])
-    lib = ctypes.CDLL(so)
+    import host_build
+    lib = ctypes.CDLL(host_build.build("grider_geom_emu"))
     lib.emu_grider_capacities.argtypes = [ctypes.c_int, ctypes.c_float] + [ctypes.c_int] * 4 + [ctypes.c_void_p]
     out = (ctypes.c_longlong * 3)()
     rc = lib.emu_grider_capacities(HANDLE_CFG[0], HANDLE_CFG[1], HANDLE_CFG[2], HANDLE_W, HANDLE_H, max_batch, ctypes.addressof(out))

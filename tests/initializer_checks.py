@@ -2,14 +2,12 @@
 (tests/emu/initializer_emu.cpp), one way of running a call on either the library or the host build, and the comparisons."""
 import ctypes
 import functools
-import os
-import subprocess
 
 import numpy as np
 
+import host_build
 import initializer_model as im
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CAM = (458.0, 458.0, 376.0, 240.0)
 WIDTH, HEIGHT = 752, 480
 EXTRA_REFERENCE_KEYS = 40   # unmatched keys of the reference frame: Normalize runs over all keys, not only the matched ones
@@ -71,13 +69,7 @@ class Emu:
 
     def __init__(self):
         if Emu._lib is None:
-            src = os.path.join(ROOT, "tests", "emu", "initializer_emu.cpp")
-            lib = os.path.join(ROOT, "tests", "emu", "libinitializer_emu.so")
-            deps = [src, os.path.join(ROOT, "include", "uvo", "uvo.h")] + [os.path.join(ROOT, "u-vip-slam_amd", "csrc", h) for h in
-                                                                           ("epnp_core.hpp", "pnpsolver_core.hpp", "sim3_core.hpp", "initializer_core.hpp")]
-            if not os.path.exists(lib) or max(os.path.getmtime(d) for d in deps) > os.path.getmtime(lib):
-                subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", lib, src])
-            L = ctypes.CDLL(lib)
+            L = ctypes.CDLL(host_build.build("initializer_emu"))
             vp, ci, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
             L.emu_initializer_create.argtypes = [vp, ci, vp]
             L.emu_initializer_destroy.argtypes = [vp]

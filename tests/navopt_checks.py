@@ -8,10 +8,10 @@ MEASURED ON THE MODEL (measure_spread below), never on the code under test; DESI
 import ctypes
 import math
 import os
-import subprocess
 
 import numpy as np
 
+import host_build
 import navopt_model as nm
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -59,14 +59,8 @@ class Emu:
         assert mutation is None or mutation in MUTATIONS
         self.uvo = uvo
         if mutation not in Emu._libs:
-            src = os.path.join(ROOT, "tests", "emu", "navopt_emu.cpp")
-            lib = os.path.join(ROOT, "tests", "emu", "libnavopt_emu%s.so" % ("" if mutation is None else "_" + mutation.lower()))
-            deps = [src, os.path.join(ROOT, "include", "uvo", "uvo.h")] + [os.path.join(ROOT, "u-vip-slam_amd", "csrc", h)
-                                                                           for h in ("lane_team.hpp", "sim3_core.hpp", "poseopt_core.hpp", "navopt_core.hpp")]
-            if not os.path.exists(lib) or max(os.path.getmtime(d) for d in deps) > os.path.getmtime(lib):
-                subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off"] +
-                                      (["-DNAVOPT_MUT=%d" % MUTATIONS[mutation]] if mutation else []) + ["-o", lib, src])
-            L = ctypes.CDLL(lib)
+            variant = (["-DNAVOPT_MUT=%d" % MUTATIONS[mutation]], "_" + mutation.lower()) if mutation else ()
+            L = ctypes.CDLL(host_build.build("navopt_emu", *variant))
             vp, ci, cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
             L.emu_nav_so3.argtypes = [ci, vp, vp]
             L.emu_nav_so3.restype = None

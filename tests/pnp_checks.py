@@ -2,14 +2,12 @@
 build's loader and the layers of the solvePnPRansac contract that hold for any implementation of the call,
 stated once.  Test infrastructure only."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
+import host_build
 import pnp_model as pm
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CAP = 1000
 
 
@@ -21,12 +19,7 @@ class Emu:
     """tests/emu/pnp_emu.cpp, built on first use with the library's contract: no FMA contraction."""
 
     def __init__(self):
-        src = os.path.join(ROOT, "tests", "emu", "pnp_emu.cpp")
-        lib = os.path.join(ROOT, "tests", "emu", "libpnp_emu.so")
-        hdr = os.path.join(ROOT, "u-vip-slam_amd", "csrc", "epnp_core.hpp")
-        if not os.path.exists(lib) or max(os.path.getmtime(src), os.path.getmtime(hdr)) > os.path.getmtime(lib):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", lib, src])
-        L = self.L = ctypes.CDLL(lib)
+        L = self.L = ctypes.CDLL(host_build.build("pnp_emu"))
         vp, ci, cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
         L.emu_pnp_subsets.argtypes = [ci, ci, vp, vp]
         L.emu_pnp_subsets.restype = None

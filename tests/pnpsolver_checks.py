@@ -2,15 +2,12 @@
 common: the host build's loader, a driver that runs one scripted session on any implementation of the solver set, and the layers of the
 PnPsolver contract that hold for any implementation, stated once.  Test infrastructure only."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
+import host_build
 import pnp_model as pm
 import pnpsolver_model as psm
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _p(a):
@@ -23,13 +20,7 @@ class Emu:
 
     def __init__(self):
         if Emu._lib is None:
-            src = os.path.join(ROOT, "tests", "emu", "pnpsolver_emu.cpp")
-            lib = os.path.join(ROOT, "tests", "emu", "libpnpsolver_emu.so")
-            deps = [src, os.path.join(ROOT, "include", "uvo", "uvo.h")] + [os.path.join(ROOT, "u-vip-slam_amd", "csrc", h)
-                                                                           for h in ("epnp_core.hpp", "pnpsolver_core.hpp")]
-            if not os.path.exists(lib) or max(os.path.getmtime(d) for d in deps) > os.path.getmtime(lib):
-                subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", lib, src])
-            L = ctypes.CDLL(lib)
+            L = ctypes.CDLL(host_build.build("pnpsolver_emu"))
             vp, ci, cd, cf, u32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_float, ctypes.c_uint32
             L.emu_glibc_rand.argtypes = [u32, ci, vp]
             L.emu_glibc_rand.restype = None

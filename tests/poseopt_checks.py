@@ -8,10 +8,10 @@ or x cond for the solve; none is fitted to an observed difference.  T and M of l
 import ctypes
 import math
 import os
-import subprocess
 
 import numpy as np
 
+import host_build
 import poseopt_model as pm
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -41,14 +41,8 @@ class Emu:
         assert mutation is None or mutation in MUTATIONS
         self.uvo = uvo
         if mutation not in Emu._libs:
-            src = os.path.join(ROOT, "tests", "emu", "poseopt_emu.cpp")
-            lib = os.path.join(ROOT, "tests", "emu", "libposeopt_emu%s.so" % ("" if mutation is None else "_" + mutation.lower()))
-            deps = [src, os.path.join(ROOT, "include", "uvo", "uvo.h")] + [os.path.join(ROOT, "u-vip-slam_amd", "csrc", h)
-                                                                           for h in ("epnp_core.hpp", "pnpsolver_core.hpp", "sim3_core.hpp", "poseopt_core.hpp")]
-            if not os.path.exists(lib) or max(os.path.getmtime(d) for d in deps) > os.path.getmtime(lib):
-                subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off"] +
-                                      (["-DPOSEOPT_MUT=%d" % MUTATIONS[mutation]] if mutation else []) + ["-o", lib, src])
-            L = ctypes.CDLL(lib)
+            variant = (["-DPOSEOPT_MUT=%d" % MUTATIONS[mutation]], "_" + mutation.lower()) if mutation else ()
+            L = ctypes.CDLL(host_build.build("poseopt_emu", *variant))
             vp, ci, cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
             L.emu_pose_from_T.argtypes = [vp, vp]
             L.emu_pose_to_T.argtypes = [vp, vp, vp]

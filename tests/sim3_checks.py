@@ -2,14 +2,12 @@
 the host build's loader, a driver that runs one scripted session on any implementation of the solver set, and the layers of the
 Sim3Solver contract that hold for any implementation, stated once.  Test infrastructure only."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
+import host_build
 import sim3_model as sm
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MUTATIONS = ("SIM3_MUT_OR", "SIM3_MUT_GT", "SIM3_MUT_THRESHOLD", "SIM3_MUT_DRAW")
 FIND = "find"
 
@@ -26,14 +24,8 @@ class Emu:
     def __init__(self, mutation=None):
         assert mutation is None or mutation in MUTATIONS
         if mutation not in Emu._libs:
-            src = os.path.join(ROOT, "tests", "emu", "sim3solver_emu.cpp")
-            lib = os.path.join(ROOT, "tests", "emu", "libsim3solver_emu%s.so" % ("" if mutation is None else "_" + mutation.lower()))
-            deps = [src, os.path.join(ROOT, "include", "uvo", "uvo.h")] + [os.path.join(ROOT, "u-vip-slam_amd", "csrc", h)
-                                                                           for h in ("epnp_core.hpp", "pnpsolver_core.hpp", "sim3_core.hpp")]
-            if not os.path.exists(lib) or max(os.path.getmtime(d) for d in deps) > os.path.getmtime(lib):
-                subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off"] + (["-D" + mutation] if mutation else []) +
-                                      ["-o", lib, src])
-            L = ctypes.CDLL(lib)
+            variant = (["-D" + mutation], "_" + mutation.lower()) if mutation else ()
+            L = ctypes.CDLL(host_build.build("sim3solver_emu", *variant))
             vp, ci, cf, u32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_uint32
             L.emu_sim3_derive.argtypes = [ci, vp]
             L.emu_sim3_max_error.argtypes = [cf]

@@ -16,10 +16,10 @@ measured, and they are measured on the MODEL (measure_spread), never on the code
 import ctypes
 import math
 import os
-import subprocess
 
 import numpy as np
 
+import host_build
 import sim3opt_model as sm
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -113,14 +113,8 @@ class Emu:
         assert mutation is None or mutation in MUTATIONS
         self.uvo = uvo
         if mutation not in Emu._libs:
-            src = os.path.join(ROOT, "tests", "emu", "sim3opt_emu.cpp")
-            lib = os.path.join(ROOT, "tests", "emu", "libsim3opt_emu%s.so" % ("" if mutation is None else "_" + mutation.lower()))
-            deps = [src, os.path.join(ROOT, "include", "uvo", "uvo.h")] + [os.path.join(ROOT, "u-vip-slam_amd", "csrc", h) for h in
-                                                                           ("epnp_core.hpp", "pnpsolver_core.hpp", "sim3_core.hpp", "poseopt_core.hpp", "sim3opt_core.hpp")]
-            if not os.path.exists(lib) or max(os.path.getmtime(d) for d in deps) > os.path.getmtime(lib):
-                subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off"] +
-                                      (["-DSIM3OPT_MUT=%d" % MUTATIONS[mutation]] if mutation else []) + ["-o", lib, src])
-            L = ctypes.CDLL(lib)
+            variant = (["-DSIM3OPT_MUT=%d" % MUTATIONS[mutation]], "_" + mutation.lower()) if mutation else ()
+            L = ctypes.CDLL(host_build.build("sim3opt_emu", *variant))
             vp, ci, cd, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_float
             L.emu_sim3opt_exp.argtypes, L.emu_sim3opt_exp.restype = [cd], cd
             L.emu_sim3opt_from_floats.argtypes = [vp, vp, cf, vp]

@@ -11,6 +11,7 @@ import pytest
 
 import ba_checks as pc
 import ba_model as bm
+import host_build
 
 NAMES = list(bm.SCENES)
 
@@ -109,9 +110,7 @@ def test_standalone_program_runs_the_committed_scenes():
     """tests/emu/ba_emu.cpp with its own main (the form that is run under the sanitizers) over tests/golden/ba_scenes.bin: the counts
     it prints for the committed scenes are the model's."""
     fixture = os.path.join(pc.ROOT, "tests", "golden", "ba_scenes.bin")
-    exe = os.path.join(pc.ROOT, "tests", "emu", "ba_emu")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-DBA_EMU_MAIN", "-o", exe, os.path.join(pc.ROOT, "tests", "emu", "ba_emu.cpp")])
-    out = subprocess.run([exe, fixture], capture_output=True, text=True)
+    out = subprocess.run([host_build.build("ba_emu_main"), fixture], capture_output=True, text=True)
     assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stdout[-2000:] + out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("scene ")]
     assert len(lines) == len(NAMES)

@@ -7,25 +7,19 @@ import subprocess
 import numpy as np
 import pytest
 
+import host_build
 import oracle_lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DRIVER = os.path.join(ROOT, "tests", "cpp", "compat_driver")
 
 
 def build_driver():
-    src = os.path.join(ROOT, "tests", "cpp", "compat_driver.cpp")
-    hdrs = [os.path.join(ROOT, "include", "uvo", "compat", f) for f in ("ORBextractor.h", "ORBmatcher.h")] + [os.path.join(ROOT, "include", "uvo", "uvo.h")]
-    if not os.path.exists(DRIVER) or max(os.path.getmtime(p) for p in [src] + hdrs) > os.path.getmtime(DRIVER):
-        subprocess.check_call(["g++", "-std=c++11", "-O2", "-Wall", "-I" + os.path.join(ROOT, "include"), src, "-o", DRIVER,
-                               "-L" + os.path.join(ROOT, "u-vip-slam_amd"), "-luvo", "-Wl,-rpath,$ORIGIN/../../u-vip-slam_amd"])
-    return DRIVER
+    return host_build.build("compat_driver")
 
 
 def test_adaptor_headers_compile_as_cxx11():
     """The reference is built as C++11 (CMakeLists.txt:16); the adaptors must compile in that dialect with plain g++."""
-    build_driver()
-    assert os.path.exists(DRIVER)
+    assert os.path.exists(build_driver())
 
 
 def test_opencv_signature_branches_type_check():
@@ -46,7 +40,6 @@ def test_opencv_signature_branches_type_check():
 
 @pytest.mark.gpu
 def test_cpp_adaptors_match_oracle(tmp_path, oracle, synth):
-    build_driver()
     w, h = 752, 480
     img = synth.make_frame(31337, w, h)
     oe = oracle.extractor(1000, 1.2, 8, 7)
@@ -69,7 +62,7 @@ def test_cpp_adaptors_match_oracle(tmp_path, oracle, synth):
     with open(mp_p, "wb") as f:
         for i in range(M):
             f.write(struct.pack("<ffifB", px[i], py[i], level[i], vc[i], inview[i]) + mp_desc[i].tobytes())
-    r = subprocess.run([DRIVER, str(img_p), str(w), str(h), str(mp_p), str(out_p)], capture_output=True, text=True)
+    r = subprocess.run([build_driver(), str(img_p), str(w), str(h), str(mp_p), str(out_p)], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     raw = open(out_p, "rb").read()
     n_g = struct.unpack_from("<i", raw, 0)[0]

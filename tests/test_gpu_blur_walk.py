@@ -28,13 +28,11 @@ Frames are uniform noise (every level keeps keypoints, so the oracle blurs every
 saturate).  A wrong frame stride shows in frames 1 and 2.
 """
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import host_build
 
 # (width, height, levels, frames, frames compared) -> per level (nfull, nseg, sub[0], sub[1]) at the batch's rows per segment
 CASES = {
@@ -58,11 +56,7 @@ def _rows_per_seg(frames):
 
 
 def _plan_lib():
-    lib = os.path.join(ROOT, "tests", "emu", "libblur_plan_emu.so")
-    srcs = [os.path.join(ROOT, "tests", "emu", "blur_plan_emu.cpp"), os.path.join(ROOT, "u-vip-slam_amd", "csrc", "strip_plan.hpp")]
-    if not os.path.exists(lib) or max(os.path.getmtime(p) for p in srcs) > os.path.getmtime(lib):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", lib, srcs[0]])
-    E = ctypes.CDLL(lib)
+    E = ctypes.CDLL(host_build.build("blur_plan_emu"))
     E.emu_strip_plan.argtypes = [ctypes.c_int] * 3 + [ctypes.c_void_p]
     return E
 

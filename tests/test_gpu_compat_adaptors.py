@@ -14,10 +14,9 @@ import numpy as np
 import pytest
 
 import compat_model as cm
+import host_build
 import oracle_lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DRIVER = os.path.join(ROOT, "tests", "cpp", "compat_scenes")
 TAKEN = 0x7FFFFFFF
 W, H = 752, 480
 INTR_A = (458.654, 457.296, 367.215, 248.375)                  # Data/Settings_VIORB.yaml
@@ -29,19 +28,12 @@ DIST = (-0.28340811, 0.07395907)
 
 
 def build_scenes_driver():
-    src = os.path.join(ROOT, "tests", "cpp", "compat_scenes.cpp")
-    deps = [src, os.path.join(ROOT, "include", "uvo", "uvo.h")] + \
-        [os.path.join(ROOT, "include", "uvo", "compat", f) for f in ("ORBextractor.h", "ORBmatcher.h", "Grider_FAST.h")]
-    if not os.path.exists(DRIVER) or max(os.path.getmtime(p) for p in deps) > os.path.getmtime(DRIVER):
-        subprocess.check_call(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), src, "-o", DRIVER,
-                               "-L" + os.path.join(ROOT, "u-vip-slam_amd"), "-luvo", "-Wl,-rpath,$ORIGIN/../../u-vip-slam_amd"])
-    return DRIVER
+    return host_build.build("compat_scenes")
 
 
 def test_scene_driver_compiles_warning_free():
     """-std=c++11 -Wall -Werror, without a GPU"""
-    build_scenes_driver()
-    assert os.path.exists(DRIVER)
+    assert os.path.exists(build_scenes_driver())
 
 
 # ---------------------------------------------------------------------------------------------------------------------------- scene
@@ -813,14 +805,13 @@ OP_NAMES = {v: k for k, v in globals().items() if k.startswith("OP_")}
 
 @pytest.fixture(scope="module")
 def scene_run(tmp_path_factory, oracle, synth):
-    build_scenes_driver()
     sc, ids = build_scene(oracle, synth)
     add_calls(sc, ids)
     ex = Expect(oracle, sc, ids)
     exp = ex.run()
     d = tmp_path_factory.mktemp("scenes")
     sc.write(str(d / "scene.bin"))
-    r = subprocess.run([DRIVER, str(d / "scene.bin"), str(d / "dump.txt")], capture_output=True, text=True, timeout=240)
+    r = subprocess.run([build_scenes_driver(), str(d / "scene.bin"), str(d / "dump.txt")], capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stdout + r.stderr
     return sc, ex, exp, parse_dump(str(d / "dump.txt")), r.stderr
 

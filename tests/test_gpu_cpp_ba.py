@@ -13,27 +13,20 @@ import numpy as np
 import pytest
 
 import ba_model as bm
+import host_build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DRIVER = os.path.join(ROOT, "tests", "cpp", "compat_ba")
 INV_SIGMA2 = (1.0 / (np.float32(1.2) ** np.arange(8)) ** 2).astype(np.float32)
 UNSET = 1000000
 IDS = [3, 0, 5, 6, 7, 8, 9, 10, 11]        # mnId of key frame k: key frame 1, a local one, is the map's first
 
 
 def build_driver():
-    src = os.path.join(ROOT, "tests", "cpp", "compat_ba.cpp")
-    hdrs = [os.path.join(ROOT, "include", "uvo", "compat", "Optimizer.h"), os.path.join(ROOT, "include", "uvo", "uvo.h")]
-    if not os.path.exists(DRIVER) or max(os.path.getmtime(p) for p in [src] + hdrs) > os.path.getmtime(DRIVER):
-        subprocess.check_call(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), src, "-o", DRIVER,
-                               "-L" + os.path.join(ROOT, "u-vip-slam_amd"), "-luvo", "-Wl,-rpath,$ORIGIN/../../u-vip-slam_amd"])
-    return DRIVER
+    return host_build.build("compat_ba")
 
 
 def test_ba_driver_compiles_as_cxx11(uvo):
     """The adaptors instantiate over key-frame / map-point / map stand-ins in the reference's dialect, warnings as errors."""
-    build_driver()
-    assert os.path.exists(DRIVER)
+    assert os.path.exists(build_driver())
 
 
 def graph():
@@ -161,10 +154,9 @@ def gather_local(kfs, mps, cur):
 
 
 def run(tmp_path, kfs, mps, **kw):
-    build_driver()
     scene, out = str(tmp_path / "scene.bin"), str(tmp_path / "out.bin")
     write_scene(scene, kfs, mps, **kw)
-    r = subprocess.run([DRIVER, scene, out], capture_output=True, text=True, timeout=120)
+    r = subprocess.run([build_driver(), scene, out], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, (r.returncode, r.stdout[-1000:], r.stderr[-1000:])
     return read_out(out, kfs, mps)
 

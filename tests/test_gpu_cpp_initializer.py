@@ -9,32 +9,22 @@ import subprocess
 import numpy as np
 import pytest
 
+import host_build
 import initializer_checks as ic
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DRIVER = os.path.join(ROOT, "tests", "cpp", "compat_initializer")
 
 
 def build_driver():
-    src = os.path.join(ROOT, "tests", "cpp", "compat_initializer.cpp")
-    hdrs = [os.path.join(ROOT, "include", "uvo", "compat", "Initializer.h"), os.path.join(ROOT, "include", "uvo", "uvo.h")]
-    if not os.path.exists(DRIVER) or max(os.path.getmtime(p) for p in [src] + hdrs) > os.path.getmtime(DRIVER):
-        subprocess.check_call(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                               "-I" + os.path.join(ROOT, "tests", "cpp", "opencv_decl_stub"), src, "-o", DRIVER,
-                               "-L" + os.path.join(ROOT, "u-vip-slam_amd"), "-luvo", "-Wl,-rpath,$ORIGIN/../../u-vip-slam_amd"])
-    return DRIVER
+    return host_build.build("compat_initializer")
 
 
 def test_initializer_driver_compiles_as_cxx11(uvo):
     """The adaptor instantiates over a frame stand-in in the reference's dialect, warnings as errors."""
-    build_driver()
-    assert os.path.exists(DRIVER)
+    assert os.path.exists(build_driver())
 
 
 @pytest.mark.gpu
 def test_cpp_initialize_equals_the_c_abi(uvo, tmp_path):
     """Two scenes on one reference frame and one generator: a general one (accepted) and its pure-rotation twin (rejected)."""
-    build_driver()
     k1, k2a, m12, _ = ic.scene(0, 64, 0.1)
     _, k2b, _, _ = ic.scene(0, 64, 0.1, "rotation")
     blob = struct.pack("<ii4f", len(k1), 2, *ic.CAM) + k1.tobytes()
@@ -43,7 +33,7 @@ def test_cpp_initialize_equals_the_c_abi(uvo, tmp_path):
     scene_p, out_p = str(tmp_path / "scene.bin"), str(tmp_path / "out.bin")
     with open(scene_p, "wb") as f:
         f.write(blob)
-    r = subprocess.run([DRIVER, scene_p, out_p], capture_output=True, text=True)
+    r = subprocess.run([build_driver(), scene_p, out_p], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     raw = open(out_p, "rb").read()
     klt = uvo.KLT(64, 64, max_points=256)

@@ -7,27 +7,19 @@ import subprocess
 
 import pytest
 
+import host_build
 import kfdb_cases as kc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DRIVER = os.path.join(ROOT, "tests", "cpp", "compat_kfdb")
 NAMES = sorted(kc.cases())
 
 
 def build_driver():
-    src = os.path.join(ROOT, "tests", "cpp", "compat_kfdb.cpp")
-    hdrs = [os.path.join(ROOT, "include", "uvo", "compat", "KeyFrameDatabase.h"), os.path.join(ROOT, "include", "uvo", "uvo.h"),
-            os.path.join(ROOT, "tests", "emu", "kfdb_script.hpp")]
-    if not os.path.exists(DRIVER) or max(os.path.getmtime(p) for p in [src] + hdrs) > os.path.getmtime(DRIVER):
-        subprocess.check_call(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), src, "-o", DRIVER,
-                               "-L" + os.path.join(ROOT, "u-vip-slam_amd"), "-luvo", "-Wl,-rpath,$ORIGIN/../../u-vip-slam_amd"])
-    return DRIVER
+    return host_build.build("compat_kfdb")
 
 
 def test_kfdb_driver_compiles_as_cxx11(uvo):
     """The adaptor instantiates over key frame / frame stand-ins in the reference's dialect, warnings as errors."""
-    build_driver()
-    assert os.path.exists(DRIVER)
+    assert os.path.exists(build_driver())
 
 
 @pytest.mark.gpu

@@ -11,27 +11,20 @@ import subprocess
 import numpy as np
 import pytest
 
+import host_build
 import navopt_model as nm
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DRIVER = os.path.join(ROOT, "tests", "cpp", "compat_navopt")
 INV_LEVELS = (1.0 / (1.2 ** np.arange(8)) ** 2).astype(np.float32)
 DEPTH_COV = 0.05
 
 
 def build_driver():
-    src = os.path.join(ROOT, "tests", "cpp", "compat_navopt.cpp")
-    hdrs = [os.path.join(ROOT, "include", "uvo", "compat", "Optimizer.h"), os.path.join(ROOT, "include", "uvo", "uvo.h")]
-    if not os.path.exists(DRIVER) or max(os.path.getmtime(p) for p in [src] + hdrs) > os.path.getmtime(DRIVER):
-        subprocess.check_call(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), src, "-o", DRIVER,
-                               "-L" + os.path.join(ROOT, "u-vip-slam_amd"), "-luvo", "-Wl,-rpath,$ORIGIN/../../u-vip-slam_amd"])
-    return DRIVER
+    return host_build.build("compat_navopt")
 
 
 def test_navopt_driver_compiles_as_cxx11(uvo):
     """Both overloads instantiate over frame / key frame / NavState / preintegration stand-ins in the reference's dialect, warnings as errors."""
-    build_driver()
-    assert os.path.exists(DRIVER)
+    assert os.path.exists(build_driver())
 
 
 def depth_info(sc, last):
@@ -89,7 +82,6 @@ def check_call(got, res, idx, before, idx_l, before_l, marg):
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["kf_shift_300", "fr_shift_300", "fr_shift_60"])
 def test_cpp_nav_pose_optimization(uvo, tmp_path, name):
-    build_driver()
     sc = nm.make(name)
     frame = sc["form"] == nm.FRAME
     # what the adaptor reads through float members: the intrinsics and gw
@@ -105,7 +97,7 @@ def test_cpp_nav_pose_optimization(uvo, tmp_path, name):
     scene_p, out_p = str(tmp_path / "scene.bin"), str(tmp_path / "out.bin")
     with open(scene_p, "wb") as f:
         f.write(nm.record(sc).tobytes() + struct.pack("<d", DEPTH_COV) + INV_LEVELS.tobytes() + blob_c + blob_l)
-    r = subprocess.run([DRIVER, scene_p, out_p], capture_output=True, text=True)
+    r = subprocess.run([build_driver(), scene_p, out_p], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     said = json.loads(r.stdout.strip().splitlines()[-1])
     raw = open(out_p, "rb").read()

@@ -8,36 +8,27 @@ import subprocess
 import numpy as np
 import pytest
 
+import host_build
 import triangulation_model as tm
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DRIVER = os.path.join(ROOT, "tests", "cpp", "compat_newpoints")
-
-
 def build_driver():
-    src = os.path.join(ROOT, "tests", "cpp", "compat_newpoints.cpp")
-    hdrs = [os.path.join(ROOT, "include", "uvo", "compat", "ORBmatcher.h"), os.path.join(ROOT, "include", "uvo", "uvo.h")]
-    if not os.path.exists(DRIVER) or max(os.path.getmtime(p) for p in [src] + hdrs) > os.path.getmtime(DRIVER):
-        subprocess.check_call(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), src, "-o", DRIVER,
-                               "-L" + os.path.join(ROOT, "u-vip-slam_amd"), "-luvo", "-Wl,-rpath,$ORIGIN/../../u-vip-slam_amd"])
-    return DRIVER
+    return host_build.build("compat_newpoints")
 
 
 def test_new_points_driver_compiles_as_cxx11(uvo):
     """The new adaptor member instantiates with stand-in key frame types in the reference's dialect, warnings as errors."""
-    build_driver()
-    assert os.path.exists(DRIVER)
+    assert os.path.exists(build_driver())
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("ori", [False, True])
 @pytest.mark.parametrize("name", ["twenty_pairs", "twenty_pairs_b"])
 def test_cpp_create_new_map_points(uvo, tmp_path, name, ori):
-    build_driver()
+    driver = build_driver()
     sc = tm.make_scene(**tm.SCENES[name])
     scene_p, out_p = str(tmp_path / "scene.bin"), str(tmp_path / "out.bin")
     tm.write_scene_file(scene_p, sc, ori)
-    r = subprocess.run([DRIVER, scene_p, out_p], capture_output=True, text=True)
+    r = subprocess.run([driver, scene_p, out_p], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     info = json.loads(r.stdout.strip().splitlines()[-1])
     one, host = tm.read_new_points_file(out_p, len(sc["pairs"]))

@@ -9,38 +9,29 @@ import subprocess
 import numpy as np
 import pytest
 
+import host_build
 import pnp_model as pm
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DRIVER = os.path.join(ROOT, "tests", "cpp", "compat_pnp")
 
 
 def build_driver():
-    src = os.path.join(ROOT, "tests", "cpp", "compat_pnp.cpp")
-    hdrs = [os.path.join(ROOT, "include", "uvo", "compat", "SolvePnPRansac.h"), os.path.join(ROOT, "include", "uvo", "uvo.h")]
-    if not os.path.exists(DRIVER) or max(os.path.getmtime(p) for p in [src] + hdrs) > os.path.getmtime(DRIVER):
-        subprocess.check_call(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), src, "-o", DRIVER,
-                               "-L" + os.path.join(ROOT, "u-vip-slam_amd"), "-luvo", "-Wl,-rpath,$ORIGIN/../../u-vip-slam_amd"])
-    return DRIVER
+    return host_build.build("compat_pnp")
 
 
 def test_pnp_driver_compiles_as_cxx11(uvo):
     """The adaptor instantiates over Point3f / Point2f stand-ins in the reference's dialect, warnings as errors."""
-    build_driver()
-    assert os.path.exists(DRIVER)
+    assert os.path.exists(build_driver())
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("sc", [(31, 400, 0.7, 1.0, pm.EUROC), (32, 64, 0.5, 0.3, pm.PLAIN), (33, 5, 1.0, 0.3, pm.EUROC), (34, 4, 1.0, 0.3, pm.PLAIN),
                                 (35, 20, 0.3, 1.0, pm.EUROC)], ids=lambda s: "n%d_r%.2f" % (s[1], s[2]))
 def test_cpp_solve_pnp_ransac(uvo, tmp_path, sc):
-    build_driver()
     cam, obj, img, _, _, _ = pm.scene(*sc)
     scene_p, out_p = str(tmp_path / "scene.bin"), str(tmp_path / "out.bin")
     with open(scene_p, "wb") as f:
         f.write(struct.pack("<ii4f8f", len(obj), cam.n_dist, cam.fx, cam.fy, cam.cx, cam.cy, *cam.k))
         f.write(obj.astype(np.float32).tobytes() + img.astype(np.float32).tobytes())
-    r = subprocess.run([DRIVER, scene_p, out_p], capture_output=True, text=True)
+    r = subprocess.run([build_driver(), scene_p, out_p], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     said = json.loads(r.stdout.strip().splitlines()[-1])
     raw = open(out_p, "rb").read()

@@ -10,26 +10,19 @@ import subprocess
 import numpy as np
 import pytest
 
+import host_build
 import pnpsolver_model as psm
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DRIVER = os.path.join(ROOT, "tests", "cpp", "compat_pnpsolver")
 LEVELS = (np.float32(1.2) ** (2 * np.arange(8))).astype(np.float32)
 
 
 def build_driver():
-    src = os.path.join(ROOT, "tests", "cpp", "compat_pnpsolver.cpp")
-    hdrs = [os.path.join(ROOT, "include", "uvo", "compat", "PnPsolver.h"), os.path.join(ROOT, "include", "uvo", "uvo.h")]
-    if not os.path.exists(DRIVER) or max(os.path.getmtime(p) for p in [src] + hdrs) > os.path.getmtime(DRIVER):
-        subprocess.check_call(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), src, "-o", DRIVER,
-                               "-L" + os.path.join(ROOT, "u-vip-slam_amd"), "-luvo", "-Wl,-rpath,$ORIGIN/../../u-vip-slam_amd"])
-    return DRIVER
+    return host_build.build("compat_pnpsolver")
 
 
 def test_pnpsolver_driver_compiles_as_cxx11(uvo):
     """The adaptor instantiates over frame / map point stand-ins in the reference's dialect, warnings as errors."""
-    build_driver()
-    assert os.path.exists(DRIVER)
+    assert os.path.exists(build_driver())
 
 
 def _scene(spec):
@@ -62,12 +55,11 @@ def _scene(spec):
                                   ((51, 15, 0.2), (52, 20, 0.2), (53, 10, 0.3)),                    # nobody does: all discarded
                                   ((61, 64, 0.8),)], ids=("third_returns", "all_exhausted", "single"))
 def test_cpp_relocalisation_loop(uvo, tmp_path, spec):
-    build_driver()
     cands, nkeys, blob = _scene(spec)
     scene_p, out_p = str(tmp_path / "scene.bin"), str(tmp_path / "out.bin")
     with open(scene_p, "wb") as f:
         f.write(blob)
-    r = subprocess.run([DRIVER, scene_p, out_p], capture_output=True, text=True)
+    r = subprocess.run([build_driver(), scene_p, out_p], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     said = json.loads(r.stdout.strip().splitlines()[-1])
     raw = open(out_p, "rb").read()

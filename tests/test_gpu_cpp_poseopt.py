@@ -10,32 +10,24 @@ import subprocess
 import numpy as np
 import pytest
 
+import host_build
 import poseopt_model as pm
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DRIVER = os.path.join(ROOT, "tests", "cpp", "compat_poseopt")
 INV_LEVELS = (1.0 / (1.2 ** np.arange(8)) ** 2).astype(np.float32)
 
 
 def build_driver():
-    src = os.path.join(ROOT, "tests", "cpp", "compat_poseopt.cpp")
-    hdrs = [os.path.join(ROOT, "include", "uvo", "compat", "Optimizer.h"), os.path.join(ROOT, "include", "uvo", "uvo.h")]
-    if not os.path.exists(DRIVER) or max(os.path.getmtime(p) for p in [src] + hdrs) > os.path.getmtime(DRIVER):
-        subprocess.check_call(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), src, "-o", DRIVER,
-                               "-L" + os.path.join(ROOT, "u-vip-slam_amd"), "-luvo", "-Wl,-rpath,$ORIGIN/../../u-vip-slam_amd"])
-    return DRIVER
+    return host_build.build("compat_poseopt")
 
 
 def test_poseopt_driver_compiles_as_cxx11(uvo):
     """The adaptor instantiates over frame / map point stand-ins in the reference's dialect, warnings as errors."""
-    build_driver()
-    assert os.path.exists(DRIVER)
+    assert os.path.exists(build_driver())
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["shift_100_2", "thin_12", "few_9"])
 def test_cpp_pose_optimization(uvo, tmp_path, name):
-    build_driver()
     p3d, p2d, w, K, Tcw = pm.make(name)
     n = len(p3d)
     g = np.random.default_rng(5)
@@ -54,7 +46,7 @@ def test_cpp_pose_optimization(uvo, tmp_path, name):
     scene_p, out_p = str(tmp_path / "scene.bin"), str(tmp_path / "out.bin")
     with open(scene_p, "wb") as f:
         f.write(blob)
-    r = subprocess.run([DRIVER, scene_p, out_p], capture_output=True, text=True)
+    r = subprocess.run([build_driver(), scene_p, out_p], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     said = json.loads(r.stdout.strip().splitlines()[-1])
     raw = open(out_p, "rb").read()

@@ -11,10 +11,9 @@ import subprocess
 import numpy as np
 import pytest
 
+import host_build
 import sim3opt_model as sm
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DRIVER = os.path.join(ROOT, "tests", "cpp", "compat_sim3opt")
 _SIG = np.float32(1.2) ** np.arange(8)
 SIGMA2 = (_SIG * _SIG).astype(np.float32)
 INV_SIGMA2 = (1.0 / (_SIG * _SIG)).astype(np.float32)
@@ -22,18 +21,12 @@ REC = np.dtype([("kind", "<i4"), ("xw", "<f4", 3), ("kp", "<f4", 2), ("octave", 
 
 
 def build_driver():
-    src = os.path.join(ROOT, "tests", "cpp", "compat_sim3opt.cpp")
-    hdrs = [os.path.join(ROOT, "include", "uvo", "compat", "Optimizer.h"), os.path.join(ROOT, "include", "uvo", "uvo.h")]
-    if not os.path.exists(DRIVER) or max(os.path.getmtime(p) for p in [src] + hdrs) > os.path.getmtime(DRIVER):
-        subprocess.check_call(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), src, "-o", DRIVER,
-                               "-L" + os.path.join(ROOT, "u-vip-slam_amd"), "-luvo", "-Wl,-rpath,$ORIGIN/../../u-vip-slam_amd"])
-    return DRIVER
+    return host_build.build("compat_sim3opt")
 
 
 def test_sim3opt_driver_compiles_as_cxx11(uvo):
     """The adaptor instantiates over key-frame / map-point stand-ins in the reference's dialect, warnings as errors."""
-    build_driver()
-    assert os.path.exists(DRIVER)
+    assert os.path.exists(build_driver())
 
 
 def kf_bytes(kf):
@@ -42,7 +35,6 @@ def kf_bytes(kf):
 
 @pytest.mark.gpu
 def test_cpp_optimize_sim3(uvo, tmp_path):
-    build_driver()
     base = sm.scene(seed=700, n=40, shifted2=6)
     n = 40
     # candidate 0: the scene; 1: the same pairs from another start and with other pairs shifted; 2: key frame 2 of an unrelated scene --
@@ -83,7 +75,7 @@ def test_cpp_optimize_sim3(uvo, tmp_path):
     scene_p, out_p = str(tmp_path / "scene.bin"), str(tmp_path / "out.bin")
     with open(scene_p, "wb") as f:
         f.write(blob)
-    r = subprocess.run([DRIVER, scene_p, out_p], capture_output=True, text=True)
+    r = subprocess.run([build_driver(), scene_p, out_p], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     assert json.loads(r.stdout.strip().splitlines()[-1])["candidates"] == 3
     raw = open(out_p, "rb").read()

@@ -10,26 +10,19 @@ import subprocess
 import numpy as np
 import pytest
 
+import host_build
 import sim3_model as sm
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DRIVER = os.path.join(ROOT, "tests", "cpp", "compat_sim3solver")
 LEVELS = (np.float32(1.2) ** (2 * np.arange(8))).astype(np.float32)
 
 
 def build_driver():
-    src = os.path.join(ROOT, "tests", "cpp", "compat_sim3solver.cpp")
-    hdrs = [os.path.join(ROOT, "include", "uvo", "compat", "Sim3Solver.h"), os.path.join(ROOT, "include", "uvo", "uvo.h")]
-    if not os.path.exists(DRIVER) or max(os.path.getmtime(p) for p in [src] + hdrs) > os.path.getmtime(DRIVER):
-        subprocess.check_call(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), src, "-o", DRIVER,
-                               "-L" + os.path.join(ROOT, "u-vip-slam_amd"), "-luvo", "-Wl,-rpath,$ORIGIN/../../u-vip-slam_amd"])
-    return DRIVER
+    return host_build.build("compat_sim3solver")
 
 
 def test_sim3solver_driver_compiles_as_cxx11(uvo):
     """The adaptor instantiates over key frame / map point stand-ins in the reference's dialect, warnings as errors."""
-    build_driver()
-    assert os.path.exists(DRIVER)
+    assert os.path.exists(build_driver())
 
 
 def _scene(spec, accept):
@@ -61,12 +54,11 @@ def _scene(spec, accept):
                                          (((51, 3, 0.0, 0.5), (52, 4, 0.0, 0.5)), 1000),                                         # nobody is accepted: all discarded
                                          (((61, 64, 0.8, 0.5),), 3)], ids=("third_returns", "rejected_then_accepted", "all_exhausted", "single"))
 def test_cpp_compute_sim3_loop(uvo, tmp_path, spec, accept):
-    build_driver()
     cands, nkeys, blob = _scene(spec, accept)
     scene_p, out_p = str(tmp_path / "scene.bin"), str(tmp_path / "out.bin")
     with open(scene_p, "wb") as f:
         f.write(blob)
-    r = subprocess.run([DRIVER, scene_p, out_p], capture_output=True, text=True)
+    r = subprocess.run([build_driver(), scene_p, out_p], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     said = json.loads(r.stdout.strip().splitlines()[-1])
     raw = open(out_p, "rb").read()

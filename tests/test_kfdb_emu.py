@@ -4,24 +4,14 @@ tests/kfdb_cases.py -- candidate lists and their order, the table of listed keyf
 fields of every slot after every query.  The closed-form list order (first common word, add sequence) is the host build's and the
 kernels'; the model walks an inverted file.  The same program runs once more built with the address and undefined-behaviour sanitizers."""
 import ctypes
-import os
 import subprocess
 
 import pytest
 
+import host_build
 import kfdb_cases as kc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
-SRC = [os.path.join(EMU_DIR, "kfdb_emu.cpp"), os.path.join(EMU_DIR, "kfdb_script.hpp"), os.path.join(ROOT, "u-vip-slam_amd", "csrc", "kfdb_core.hpp"),
-       os.path.join(ROOT, "include", "uvo", "uvo.h")]
 NAMES = sorted(kc.cases())
-
-
-def build_emu(out, extra=()):
-    if not os.path.exists(out) or max(os.path.getmtime(p) for p in SRC) > os.path.getmtime(out):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror", *extra, "-o", out, SRC[0]])
-    return out
 
 
 def run_emu(exe, case, tmp_path):
@@ -34,12 +24,12 @@ def run_emu(exe, case, tmp_path):
 
 @pytest.fixture(scope="module")
 def emu():
-    return build_emu(os.path.join(EMU_DIR, "kfdb_emu"))
+    return host_build.build("kfdb_emu")
 
 
 @pytest.fixture(scope="module")
-def emu_sanitized(tmp_path_factory):
-    return build_emu(str(tmp_path_factory.mktemp("kfdb_san") / "kfdb_emu_san"), ("-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"))
+def emu_sanitized():
+    return host_build.build("kfdb_emu", ("-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"), "_san")
 
 
 def test_new_symbols_are_declared_and_exported(uvo):

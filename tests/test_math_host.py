@@ -1,25 +1,17 @@
 """The scalar numerics the HIP kernels use (csrc/uvo_math.hpp), compiled for the host and compared bit-for-bit with
 what the reference calls: libm sinf/cosf (src/ORBextractor.cc:160-161), cv::fastAtan2, cvRound (via the oracle)."""
 import ctypes
-import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import host_build
 
 
 @pytest.fixture(scope="module")
 def mh():
-    src = os.path.join(ROOT, "tests", "emu", "math_host.cpp")
-    lib = os.path.join(ROOT, "tests", "emu", "libmath_host.so")
-    hdr = os.path.join(ROOT, "u-vip-slam_amd", "csrc", "uvo_math.hpp")
-    if not os.path.exists(lib) or max(os.path.getmtime(src), os.path.getmtime(hdr)) > os.path.getmtime(lib):
-        # same contract as the device build: no FMA contraction
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", lib, src, "-lpthread"])
-    L = ctypes.CDLL(lib)
+    L = ctypes.CDLL(host_build.build("math_host"))      # same contract as the device build: no FMA contraction
     L.mh_sincosf.argtypes = [ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p]
     L.mh_fast_atan2.restype = ctypes.c_float
     L.mh_fast_atan2.argtypes = [ctypes.c_float, ctypes.c_float]

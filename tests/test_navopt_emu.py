@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import host_build
 import navopt_checks as nc
 import navopt_model as nm
 
@@ -139,9 +140,7 @@ def test_stand_alone_program_runs_the_committed_scene_list():
     """tests/emu/navopt_emu.cpp with its own main (the form that is run under the sanitizers) over tests/golden/navopt_scenes.bin: the
     program's counts are the model's."""
     fixture = os.path.join(nc.ROOT, "tests", "golden", "navopt_scenes.bin")
-    exe = os.path.join(nc.ROOT, "tests", "emu", "navopt_emu")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-DNAVOPT_EMU_MAIN", "-o", exe, os.path.join(nc.ROOT, "tests", "emu", "navopt_emu.cpp")])
-    r = subprocess.run([exe, fixture], capture_output=True, text=True)
+    r = subprocess.run([host_build.build("navopt_emu_main"), fixture], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     rows = re.findall(r"^scene (\d+) form (\d) n (\d+) \+ (\d+) inliers (\d+) rounds (\d+)", r.stdout, re.M)
     assert len(rows) == len(NAMES)

@@ -2,12 +2,12 @@
 so every answer here is hand-derivable from the reference sources, or cross-checked by an independent numpy
 formulation written in this file, or for CLAHE in tests/side_model.py)."""
 import ctypes
-import subprocess
 import os
 
 import numpy as np
 import pytest
 
+import host_build
 from side_model import clahe as _clahe_numpy   # the numpy statement of OpenCV 3.4's 8-bit CLAHE, kept with the other models
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -303,13 +303,7 @@ def test_octree_toy_cases(oracle):
 
 
 def _octree_emu():
-    lib = os.path.join(ROOT, "tests", "emu", "liboctree_emu.so")
-    srcs = [os.path.join(ROOT, "tests", "emu", "octree_emu.cpp"), os.path.join(ROOT, "u-vip-slam_amd", "csrc", "octree_core.hpp"),
-            os.path.join(ROOT, "u-vip-slam_amd", "csrc", "octree_pyramid.hpp")]
-    if not os.path.exists(lib) or os.path.getmtime(lib) < max(os.path.getmtime(f) for f in srcs):
-        import subprocess
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", lib, srcs[0]])
-    E = ctypes.CDLL(lib)
+    E = ctypes.CDLL(host_build.build("octree_emu"))
     E.emu_octree_algo.argtypes = [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 8 + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                                                                            ctypes.c_int]
     return E
@@ -558,11 +552,7 @@ def test_strip_plan_tiles_every_window_exactly_once():
     """Host check of the wavefront strip plan shared by k_fast_score and k_gauss7 (csrc/strip_plan.hpp, compiled with a plain C++
     compiler): every pixel of a window belongs to exactly one (item, sub-strip); the plan never needs more wavefront-rows than
     one 248-column strip per started 248 columns would."""
-    lib = os.path.join(ROOT, "tests", "emu", "libstrip_plan_emu.so")
-    srcs = [os.path.join(ROOT, "tests", "emu", "strip_plan_emu.cpp"), os.path.join(ROOT, "u-vip-slam_amd", "csrc", "strip_plan.hpp")]
-    if not os.path.exists(lib) or max(os.path.getmtime(p) for p in srcs) > os.path.getmtime(lib):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", lib, srcs[0]])
-    E = ctypes.CDLL(lib)
+    E = ctypes.CDLL(host_build.build("strip_plan_emu"))
     E.emu_strip_plan_check.argtypes = [ctypes.c_int] * 3 + [ctypes.c_void_p] * 2
     rng = np.random.default_rng(12)
     widths = list(range(1, 700)) + [int(x) for x in rng.integers(700, 4200, 150)]
@@ -660,11 +650,7 @@ def test_undistort_point_models(oracle):
 
 
 def _pyr_tiles_emu():
-    lib = os.path.join(ROOT, "tests", "emu", "libpyr_tiles_emu.so")
-    srcs = [os.path.join(ROOT, "tests", "emu", "pyr_tiles_emu.cpp"), os.path.join(ROOT, "u-vip-slam_amd", "csrc", "pyr_tiles.hpp")]
-    if not os.path.exists(lib) or max(os.path.getmtime(p) for p in srcs) > os.path.getmtime(lib):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", lib, srcs[0]])
-    E = ctypes.CDLL(lib)
+    E = ctypes.CDLL(host_build.build("pyr_tiles_emu"))
     E.emu_pyr_tiles_run.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                     ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     return E

@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import host_build
 import poseopt_checks as pc
 import poseopt_model as pm
 
@@ -141,9 +142,7 @@ def test_stand_alone_program_runs_the_committed_scene_list(tmp_path):
     for name, got in zip(NAMES, scenes):
         want = pc.model(name)[0]
         assert all(np.array_equal(np.asarray(a, np.float32), np.asarray(b, np.float32)) for a, b in zip(got, want)), name
-    exe = os.path.join(pc.ROOT, "tests", "emu", "poseopt_emu")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-DPOSEOPT_EMU_MAIN", "-o", exe, os.path.join(pc.ROOT, "tests", "emu", "poseopt_emu.cpp")])
-    r = subprocess.run([exe, fixture], capture_output=True, text=True)
+    r = subprocess.run([host_build.build("poseopt_emu_main"), fixture], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     rows = re.findall(r"^scene (\d+) n (\d+) inliers (\d+) rounds (\d+)", r.stdout, re.M)
     assert len(rows) == len(NAMES)

@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import host_build
 import sim3opt_checks as pc
 import sim3opt_model as sm
 
@@ -200,9 +201,7 @@ def test_standalone_program_runs_the_committed_scenes():
     """tests/emu/sim3opt_emu.cpp with its own main (the form that is run under the sanitizers) over tests/golden/sim3opt_scenes.bin:
     the counts it prints for the committed scenes are the model's."""
     fixture = os.path.join(pc.ROOT, "tests", "golden", "sim3opt_scenes.bin")
-    exe = os.path.join(pc.ROOT, "tests", "emu", "sim3opt_emu")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-DSIM3OPT_EMU_MAIN", "-o", exe, os.path.join(pc.ROOT, "tests", "emu", "sim3opt_emu.cpp")])
-    out = subprocess.run([exe, fixture], capture_output=True, text=True)
+    out = subprocess.run([host_build.build("sim3opt_emu_main"), fixture], capture_output=True, text=True)
     assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stdout[-2000:] + out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("scene ")]
     assert len(lines) == len(NAMES)
