@@ -17,7 +17,7 @@
 //
 // and an overload over the list of candidates that issues ONE device call; the caller takes the first candidate in order with
 // nInliers >= 10.  With it the path from loop candidate to accepted loop links nothing of the reference's Optimizer.
-// OptimizeEssentialGraph and the NavState bundle adjustments stay with the reference's Optimizer.
+// OptimizeEssentialGraph, GlobalBundleAdjustmentNavState and the initialisation optimisers stay with the reference's Optimizer.
 //
 // The two IMU overloads of Optimizer::PoseOptimization (src/Optimizer.cc:779-1103 over a key frame, :319-777 over the last frame) over
 // the C ABI's nav optimizer (uvo_nav_* in uvo/uvo.h), for Tracking::TrackWithIMU (src/Tracking.cc:1099, :1105), TrackLocalMapWithIMU
@@ -60,6 +60,28 @@
 // UpdateNormalAndDepth and the map-update flag.  Departures: pbStopFlag is read once, before the call (1 is returned and nothing is
 // optimised when it is set); the erasures of the first check and the write-back happen once, after the call and under
 // mMutexMapUpdate, not in between the two rounds.
+//
+// Optimizer::LocalBundleAdjustmentNavState(pCurKF, lLocalKeyFrames, pbStopFlag, pMap, gw, grot, pLM, ini_depth, depth_cov, fixedKF_id)
+// (src/Optimizer.cc:1105-1732, called at src/LocalMapping.cc:811 once the IMU is initialised) over the C ABI's nav bundle adjuster
+// (uvo_nav_bundle_adjust* in uvo/uvo.h):
+//
+//     - Optimizer::LocalBundleAdjustmentNavState(mpCurrentKeyFrame, mlLocalKeyFrames, &mbAbortBA, mpMap, mGravityVec, grot, this, d0, dcov, fixed_id);
+//     + USLAM::Optimizer::LocalBundleAdjustmentNavState(mpCurrentKeyFrame, mlLocalKeyFrames, &mbAbortBA, mpMap, mGravityVec, grot, this, d0, dcov, fixed_id,
+//     +                                                 navprm, navadjuster);       // a USLAM::NavParams and a USLAM::NavBundleAdjuster
+//
+// It needs of the key-frame type, besides LocalBundleAdjustment's members: GetPrevKeyFrame(), GetNavState(), GetIMUPreInt() (the getters
+// of uvo_nav_ba_link's fields), Depth_Vec and Depth_Vec_Time (size(), [i]), mTimeStamp, SetNavStatePos, SetNavStateVel, SetNavStateRot,
+// SetNavStateDeltaBg, SetNavStateDeltaBa; of NavState what the IMU overloads of PoseOptimization need.  The local key frames come as any
+// container with begin() / end() / front() / back().  The reference's effects are kept: the gathering of :1121-1182 with both marks (the
+// key frame before the window first among the fixed ones), a point's edges in the order its GetObservations() iterates, per entry of
+// Depth_Vec the forward edge when (t1 - td) < (td - t0), else the backward edge when minKFID + 1 < pKF0->mnId, else none; the erasures of
+// the FINAL check only (EraseMapPointMatch(pMP), EraseObservation(pKF)), P, V, R and the delta biases set, the pose of UpdatePoseFromNS
+// written through ba_set_pose, SetWorldPos / UpdateNormalAndDepth and the map-update flag, all under mMutexMapUpdate.  The depth entry's
+// information is computed with the 3 x 3 position block, as for the pose overloads.  Departures: pbStopFlag is read once, before the
+// call; -1 is returned, and nothing but the marks touched, when the window's first key frame has no previous key frame (the reference
+// reads pKFPrevLocal->mnId before its null test at :1149), when that key frame is bad (the reference then looks up a vertex that is not
+// there), or when the library call fails; a backward entry whose pKF_1 is not a key frame of the window is skipped (likewise).  grot is
+// taken and not read.
 //
 // The frame type needs mvpMapPoints (pointers; null where there is no map point; GetWorldPos() returning something with at<float>(i)
 // or operator[]), mvKeysUn (cv::KeyPoint layout), mvInvLevelSigma2, mvbOutlier (std::vector<bool> or anything indexable and
@@ -547,6 +569,114 @@ template <class L>
 void nav_scatter_last(NavOptimizer&, L*, long) {}
 }  // namespace detail
 
+// the owner of the device nav adjuster: one on the mapping thread's matcher handle
+class NavBundleAdjuster {
+ public:
+  NavBundleAdjuster(uvo_matcher* m, int max_free, int max_fixed, int max_points, int max_edges, int max_depth) : a_(0) {
+    uvo_nav_bundle_adjuster_create(m, max_free, max_fixed, max_points, max_edges, max_depth, &a_);
+  }
+  ~NavBundleAdjuster() { uvo_nav_bundle_adjuster_destroy(a_); }
+  bool ok() const { return a_ != 0; }
+  uvo_nav_bundle_adjuster* handle() { return a_; }
+  // gathering buffers, kept between calls so that a call allocates nothing once they have grown
+  std::vector<uvo_nav_state> states, states_out;
+  std::vector<uvo_nav_ba_link> links;
+  std::vector<uvo_nav_ba_depth> depth;
+  std::vector<float> points, obs, inv_sigma2, cameras, Tcw_out, points_out;
+  std::vector<uint8_t> fixed, has_bias, point_bad, excluded, erased;
+  std::vector<int32_t> begin, edge_kf, edge_camera, edge_index;  // edge_index: the observation's index in its key frame
+  uvo_nav_ba_result result;                                      // of the last call: counts, iterations, trials
+
+ private:
+  NavBundleAdjuster(const NavBundleAdjuster&);
+  NavBundleAdjuster& operator=(const NavBundleAdjuster&);
+  uvo_nav_bundle_adjuster* a_;
+};
+
+namespace detail {
+template <class KF>
+int index_of(const std::vector<KF*>& v, const KF* p) {
+  for (size_t i = 0; i < v.size(); ++i)
+    if (v[i] == p) return (int)i;
+  return -1;
+}
+inline void navba_clear(NavBundleAdjuster& a) {
+  a.states.clear(), a.links.clear(), a.depth.clear(), a.points.clear(), a.obs.clear(), a.inv_sigma2.clear(), a.cameras.clear(), a.fixed.clear(), a.has_bias.clear();
+  a.point_bad.clear(), a.begin.assign(1, 0), a.edge_kf.clear(), a.edge_camera.clear(), a.edge_index.clear();
+}
+template <class KF>
+void navba_add_keyframe(NavBundleAdjuster& a, KF* pKF, bool fixed, bool has_bias) {
+  a.states.push_back(uvo_nav_state());
+  nav_state_of(pKF->GetNavState(), a.states.back());
+  a.fixed.push_back(fixed ? 1 : 0), a.has_bias.push_back(has_bias ? 1 : 0);
+}
+template <class Pre>
+void navba_link(uvo_nav_ba_link& l, int kf0, int kf1, const Pre& pre) {
+  l.kf0 = kf0, l.kf1 = kf1, l.dT = pre.getDeltaTime();
+  vec3_of(pre.getDeltaP(), l.dP), vec3_of(pre.getDeltaV(), l.dV), mat3_of(pre.getDeltaR(), l.dR);
+  mat3_of(pre.getJPBiasg(), l.JPg), mat3_of(pre.getJPBiasa(), l.JPa), mat3_of(pre.getJVBiasg(), l.JVg), mat3_of(pre.getJVBiasa(), l.JVa), mat3_of(pre.getJRBiasg(), l.JRg);
+  for (int i = 0; i < 9; ++i)
+    for (int j = 0; j < 9; ++j) l.cov_pvphi[i * 9 + j] = pre.getCovPVPhi()(i, j);
+}
+template <class A, class KF>
+int navba_camera(A& a, KF* pKF) {
+  const float k[4] = {(float)pKF->fx, (float)pKF->fy, (float)pKF->cx, (float)pKF->cy};
+  const int n = (int)a.cameras.size() / 4;
+  for (int i = 0; i < n; ++i)
+    if (a.cameras[4 * i] == k[0] && a.cameras[4 * i + 1] == k[1] && a.cameras[4 * i + 2] == k[2] && a.cameras[4 * i + 3] == k[3]) return i;
+  a.cameras.insert(a.cameras.end(), k, k + 4);
+  return n;
+}
+// a point and its edges (:1498-1559): as ba_add_point
+template <class KF, class MP>
+void navba_add_point(NavBundleAdjuster& a, MP* pMP, const std::vector<KF*>& vertices, std::vector<KF*>& edge_kfs) {
+  float X[3];
+  world_pos(pMP->GetWorldPos(), X);
+  a.points.insert(a.points.end(), X, X + 3);
+  a.point_bad.push_back(pMP->isBad() ? 1 : 0);
+  const auto observations = pMP->GetObservations();
+  for (auto mit = observations.begin(); mit != observations.end(); ++mit) {
+    KF* pKFi = mit->first;
+    if (pKFi->isBad()) continue;
+    const int k = index_of(vertices, pKFi);
+    if (k < 0) continue;
+    const auto kp = pKFi->GetKeyPointUn(mit->second);
+    static_assert(sizeof(kp) == sizeof(uvo_keypoint), "keypoint layout must be cv::KeyPoint");
+    const uvo_keypoint& u = reinterpret_cast<const uvo_keypoint&>(kp);
+    a.edge_kf.push_back(k), a.obs.push_back(u.x), a.obs.push_back(u.y);
+    a.inv_sigma2.push_back(pKFi->GetInvSigma2(u.octave));
+    a.edge_camera.push_back(navba_camera(a, pKFi));
+    a.edge_index.push_back((int32_t)mit->second);
+    edge_kfs.push_back(pKFi);
+  }
+  a.begin.push_back((int32_t)a.edge_kf.size());
+}
+template <class Mat>
+int navba_call(NavBundleAdjuster& a, const NavParams& prm, const Mat& gw) {
+  const size_t K = a.fixed.size(), P = a.point_bad.size(), E = a.edge_kf.size();
+  a.states_out.assign(K + 1, uvo_nav_state()), a.Tcw_out.assign(16 * K + 1, 0.f), a.points_out.assign(3 * P + 1, 0.f), a.excluded.assign(E + 1, 0), a.erased.assign(E + 1, 0);
+  uvo_nav_ba_problem q = uvo_nav_ba_problem();
+  q.n_keyframes = (int32_t)K, q.n_points = (int32_t)P, q.n_edges = (int32_t)E, q.n_cameras = (int32_t)(a.cameras.size() / 4);
+  q.n_links = (int32_t)a.links.size(), q.n_depth = (int32_t)a.depth.size();
+  a.states.push_back(uvo_nav_state()), a.links.push_back(uvo_nav_ba_link()), a.depth.push_back(uvo_nav_ba_depth());
+  a.points.push_back(0.f), a.obs.push_back(0.f), a.inv_sigma2.push_back(0.f), a.cameras.push_back(0.f);
+  a.fixed.push_back(0), a.has_bias.push_back(0), a.point_bad.push_back(0), a.edge_kf.push_back(0), a.edge_camera.push_back(0);  // no empty vector is indexed
+  q.kf_state = &a.states[0], q.kf_fixed = &a.fixed[0], q.kf_has_bias = &a.has_bias[0], q.points = &a.points[0], q.point_bad = &a.point_bad[0];
+  q.point_edge_begin = &a.begin[0], q.edge_kf = &a.edge_kf[0], q.edge_obs = &a.obs[0], q.edge_inv_sigma2 = &a.inv_sigma2[0], q.edge_camera = &a.edge_camera[0];
+  q.cameras = &a.cameras[0], q.links = &a.links[0], q.depth = &a.depth[0];
+  float g[3];
+  world_pos(gw, g);
+  for (int i = 0; i < 3; ++i) {
+    q.gw[i] = g[i], q.Pbc[i] = prm.Tbc[i * 4 + 3];
+    for (int j = 0; j < 3; ++j) q.Rbc[i * 3 + j] = prm.Tbc[i * 4 + j];
+  }
+  q.gyr_bias_rw2 = prm.gyr_bias_rw2, q.acc_bias_rw2 = prm.acc_bias_rw2;
+  a.result = uvo_nav_ba_result();
+  a.result.kf_state = &a.states_out[0], a.result.kf_Tcw = &a.Tcw_out[0], a.result.points = &a.points_out[0], a.result.excluded = &a.excluded[0], a.result.erased = &a.erased[0];
+  return uvo_nav_bundle_adjust(a.handle(), &q, &a.result) == UVO_OK ? 0 : -1;
+}
+}  // namespace detail
+
 namespace Optimizer {
 
 // int Optimizer::PoseOptimization(FrameKTL* pFrame, KeyFrame* pLastKF, const IMUPreintegrator&, const cv::Mat& gw, const cv::Mat& grot,
@@ -770,6 +900,128 @@ int RecoveryBundleAdjustemnt(KF* pKFini, KF* pKFcur, int nIterations, bool* pbSt
   vpKFs.push_back(pKFcur);
   const auto vpMP = pKFcur->getmvpMappoints();
   return BundleAdjustment(vpKFs, vpMP, nIterations, pbStopFlag, adj);
+}
+
+// void Optimizer::LocalBundleAdjustmentNavState(KeyFrame* pCurKF, const std::list<KeyFrame*>& lLocalKeyFrames, bool* pbStopFlag, Map* pMap,
+// const cv::Mat& gw, const cv::Mat& grot, LocalMapping* pLM, double ini_depth, double depth_cov, int fixedKF_id).  Returns 0; 1 when
+// *pbStopFlag was set (the marks of the gathering are left, nothing else is touched); -1 when there is no usable key frame before the window
+// or the library call fails (likewise).
+template <class KF, class List, class Map, class Mat, class LM>
+int LocalBundleAdjustmentNavState(KF* pCurKF, const List& lLocalKeyFrames, bool* pbStopFlag, Map* pMap, const Mat& gw, const Mat& grot, LM* pLM, double ini_depth,
+                                  double depth_cov, int fixedKF_id, const NavParams& prm, NavBundleAdjuster& adj) {
+  typedef typename std::remove_pointer<typename std::remove_reference<decltype(pCurKF->GetMapPointMatches()[0])>::type>::type MP;
+  (void)grot;
+  if (!adj.ok()) return -1;
+  // All KeyFrames in Local window are optimized (:1121-1125)
+  std::vector<KF*> window(lLocalKeyFrames.begin(), lLocalKeyFrames.end());
+  if (window.empty()) return -1;
+  for (size_t l = 0; l < window.size(); ++l) window[l]->mnBALocalForKF = pCurKF->mnId;
+  // Local MapPoints seen in Local KeyFrames (:1127-1143)
+  std::vector<MP*> lLocalMapPoints;
+  for (size_t l = 0; l < window.size(); ++l) {
+    const std::vector<MP*> vpMPs = window[l]->GetMapPointMatches();
+    for (size_t v = 0; v < vpMPs.size(); ++v) {
+      MP* pMP = vpMPs[v];
+      if (pMP)
+        if (!pMP->isBad())
+          if (pMP->mnBALocalForKF != pCurKF->mnId) {
+            lLocalMapPoints.push_back(pMP);
+            pMP->mnBALocalForKF = pCurKF->mnId;
+          }
+    }
+  }
+  // Fixed Keyframes: the KeyFrame before local window, then the covisible ones (:1145-1182)
+  std::vector<KF*> lFixedCameras;
+  KF* pKFPrevLocal = window.front()->GetPrevKeyFrame();
+  if (!pKFPrevLocal) return -1;
+  const long unsigned int minKFID = pKFPrevLocal->mnId;
+  pKFPrevLocal->mnBAFixedForKF = pCurKF->mnId;
+  if (pKFPrevLocal->isBad()) return -1;
+  lFixedCameras.push_back(pKFPrevLocal);
+  for (size_t l = 0; l < lLocalMapPoints.size(); ++l) {
+    const auto observations = lLocalMapPoints[l]->GetObservations();
+    for (auto mit = observations.begin(); mit != observations.end(); ++mit) {
+      KF* pKFi = mit->first;
+      if (pKFi->mnBALocalForKF != pCurKF->mnId && pKFi->mnBAFixedForKF != pCurKF->mnId) {
+        pKFi->mnBAFixedForKF = pCurKF->mnId;
+        if (!pKFi->isBad()) lFixedCameras.push_back(pKFi);
+      }
+    }
+  }
+  if (pbStopFlag && *pbStopFlag) return 1;
+  detail::navba_clear(adj);
+  std::vector<KF*> vertices(window);
+  vertices.insert(vertices.end(), lFixedCameras.begin(), lFixedCameras.end());
+  for (size_t l = 0; l < window.size(); ++l) detail::navba_add_keyframe(adj, window[l], (long)window[l]->mnId == (long)fixedKF_id, true);
+  for (size_t l = 0; l < lFixedCameras.size(); ++l) detail::navba_add_keyframe(adj, lFixedCameras[l], true, lFixedCameras[l] == pKFPrevLocal);
+  // the inertial links and the depth entries (:1273-1482)
+  for (size_t l = 0; l < window.size(); ++l) {
+    KF* pKF1 = window[l];
+    KF* pKF0 = pKF1->GetPrevKeyFrame();
+    const int k0 = pKF0 ? detail::index_of(vertices, pKF0) : -1;
+    if (k0 < 0 || !adj.has_bias[k0]) return -1;
+    adj.links.push_back(uvo_nav_ba_link());
+    detail::navba_link(adj.links.back(), k0, (int)l, pKF1->GetIMUPreInt());
+    for (size_t i = 0; i < pKF1->Depth_Vec.size(); i++) {
+      const double depth_time = pKF1->Depth_Vec_Time[i];
+      uvo_nav_ba_depth d = uvo_nav_ba_depth();
+      KF* pRot = 0;
+      if ((pKF1->mTimeStamp - depth_time) < (depth_time - pKF0->mTimeStamp)) {      // forward
+        d.ka = (int32_t)l, d.kb = k0, d.kc = k0, d.link = (int32_t)l;
+        d.shi = (pKF1->mTimeStamp - pKF0->mTimeStamp) / (depth_time - pKF0->mTimeStamp);
+        pRot = pKF0;
+      } else if (minKFID + 1 < pKF0->mnId) {                                        // backward
+        KF* pKF_1 = pKF0->GetPrevKeyFrame();
+        const int k_1 = pKF_1 ? detail::index_of(window, pKF_1) : -1;
+        if (k_1 < 0 || k_1 >= (int)l) continue;     // its preintegration is the link of a window key frame listed before
+        d.ka = k0, d.kb = k_1, d.kc = k_1, d.link = k_1;
+        d.shi = (pKF0->mTimeStamp - pKF_1->mTimeStamp) / (depth_time - pKF_1->mTimeStamp);
+        pRot = pKF_1;
+      } else {
+        continue;
+      }
+      d.meas = pKF1->Depth_Vec[i] - ini_depth;
+      double R[9], cov3 = 0.;
+      detail::mat3_of(pRot->GetNavState().Get_RotMatrix(), R);
+      const double* cov = adj.links[d.link].cov_pvphi;
+      for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) cov3 = cov3 + (R[r * 3 + 2] * cov[r * 9 + c]) * R[c * 3 + 2];  // the 3 x 3 position block
+      const double cov1 = (d.shi * d.shi * depth_cov * depth_cov) + cov3;
+      d.info = 1 / (cov1 * cov1);
+      adj.depth.push_back(d);
+    }
+  }
+  std::vector<KF*> vpEdgeKF;
+  for (size_t l = 0; l < lLocalMapPoints.size(); ++l) detail::navba_add_point(adj, lLocalMapPoints[l], vertices, vpEdgeKF);
+  if (detail::navba_call(adj, prm, gw) != 0) return -1;
+  {
+    detail::LockGuard<decltype(pMap->mMutexMapUpdate)> lock(pMap->mMutexMapUpdate);
+    // vToErase: the final check's (:1624-1678)
+    for (size_t j = 0; j < lLocalMapPoints.size(); ++j) {
+      MP* pMP = lLocalMapPoints[j];
+      for (int e = adj.begin[j]; e < adj.begin[j + 1]; ++e)
+        if (adj.erased[e]) {
+          vpEdgeKF[e]->EraseMapPointMatch(pMP);
+          pMP->EraseObservation(vpEdgeKF[e]);
+        }
+    }
+    // Keyframes (:1680-1716)
+    for (size_t l = 0; l < window.size(); ++l) {
+      KF* pKFi = window[l];
+      typename std::decay<decltype(pKFi->GetNavState())>::type ns = pKFi->GetNavState();
+      detail::nav_state_to(adj.states_out[l], ns);
+      pKFi->SetNavStatePos(ns.Get_P()), pKFi->SetNavStateVel(ns.Get_V()), pKFi->SetNavStateRot(ns.Get_R());
+      pKFi->SetNavStateDeltaBg(ns.Get_dBias_Gyr()), pKFi->SetNavStateDeltaBa(ns.Get_dBias_Acc());
+      ba_set_pose(pKFi, &adj.Tcw_out[16 * l]);
+    }
+    // Points (:1718-1725)
+    for (size_t j = 0; j < lLocalMapPoints.size(); ++j) {
+      ba_set_world_pos(lLocalMapPoints[j], &adj.points_out[3 * j]);
+      lLocalMapPoints[j]->UpdateNormalAndDepth();
+    }
+  }
+  if (pLM) pLM->SetMapUpdateFlagInTracking(true);
+  return 0;
 }
 
 }  // namespace Optimizer

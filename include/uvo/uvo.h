@@ -1456,6 +1456,100 @@ int uvo_bundle_adjust(uvo_bundle_adjuster* a, const uvo_ba_problem* problem, uvo
 /* test tap: the trace of the adjuster's last call (no record when that call optimised nothing). */
 int uvo_bundle_adjuster_trace(uvo_bundle_adjuster* a, uvo_ba_trace* out);
 
+/* ------------------------------------------------------------------------------------------------
+ * Visual-inertial local bundle adjustment -- replaces Optimizer::LocalBundleAdjustmentNavState (src/Optimizer.cc:1105-1732, called at
+ * src/LocalMapping.cc:811 once per key frame after the IMU is initialised) with the parts of g2o and src/IMU/g2otypes.cpp it runs.
+ * Every key frame carries a uvo_nav_state; a free one has 15 unknowns (VertexNavStatePVR dP dV dPhi, then VertexNavStateBias dbg dba),
+ * in the caller's order in the reduced system.  Per LINK (kf0 -> kf1, kf1's preintegration): EdgeNavStatePVR on (PVR kf0, PVR kf1,
+ * Bias kf0), information CovPVPhi^-1, Huber (float)sqrt(21.666); EdgeNavStateBias on (Bias kf0, Bias kf1), information
+ * InvCovBgaRW / dT, Huber (float)sqrt(16.812).  Per DEPTH entry: EdgeNavStateDepthProjected on (PVR ka, PVR kb, Bias kc) with the
+ * preintegration of link `link`, Huber (float)sqrt(16.812).  Per observation: EdgeNavStatePVRPointXYZ, information invSigma2 * I,
+ * Huber (float)sqrt(5.991); the points are marginalised.
+ * optimize(5); first check: of every edge whose point is not flagged, chi2 > 5.991 (in double) or a non-positive depth puts it at
+ * level 1 (`excluded`) and the kernel comes off whatever the verdict; edges of flagged points keep kernel and level; the inertial and
+ * depth edges are never checked; optimize(10); final check over ALL edges of unflagged points, excluded ones too, on the stored chi2
+ * (for an excluded edge: what round one's last evaluation left) and the depth at the final estimates (`erased`).  An edge excluded
+ * for its depth alone can survive the final check: that is the reference's behaviour and why there are two masks.
+ * Phases are separate launches in the matcher's stream, as for uvo_bundle_adjust; nothing is allocated per call.
+ * Departures (contract 13): those of uvo_bundle_adjust and uvo_nav_optimize -- the stop flag is the adaptor's,
+ * the dense unpivoted LDL^T in the stated order stands for Eigen's sparse solver and for inverse(), every sum has one shape fixed by
+ * indices alone, sin cos atan are the library's own, SO3 is normalised where a quaternion is made -- and the depth entry's
+ * information is the caller's scalar (block(0,0,2,2) into a Matrix3d at :1392 is not defined).
+ * Agreement with the model (tests/navba_model.py) is to a tolerance; the device and the host build (tests/emu/navba_emu.cpp) agree
+ * bit for bit.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct uvo_nav_bundle_adjuster uvo_nav_bundle_adjuster;
+
+typedef struct uvo_nav_ba_link {
+  int32_t kf0, kf1;        /* pKF1->GetPrevKeyFrame() and pKF1 */
+  double dT, dP[3], dV[3], dR[9];                    /* pKF1->GetIMUPreInt(): as uvo_nav_problem */
+  double JPg[9], JPa[9], JVg[9], JVa[9], JRg[9];
+  double cov_pvphi[81];    /* getCovPVPhi(), inverted in the library */
+} uvo_nav_ba_link;
+
+typedef struct uvo_nav_ba_depth {
+  int32_t ka, kb, kc;      /* vertices: PVR of ka, PVR of kb, Bias of kc.  Forward: (pKF1, pKF0, pKF0); backward: (pKF0, pKF_1, pKF_1) */
+  int32_t link;            /* whose preintegration the edge reads.  Forward: pKF1's link; backward: pKF_1's, as :1435 has it */
+  double shi, meas, info;  /* timeshi, depth - ini_depth, the information */
+} uvo_nav_ba_depth;
+
+typedef struct uvo_nav_ba_problem {
+  int32_t n_keyframes, n_points, n_edges, n_cameras, n_links, n_depth;
+  const uvo_nav_state* kf_state;   /* [n_keyframes] GetNavState() */
+  const uint8_t* kf_fixed;         /* [n_keyframes] 1: both vertices fixed */
+  const uint8_t* kf_has_bias;      /* [n_keyframes] 1: carries a bias vertex (window key frames and pKFPrevLocal) */
+  const float* points;             /* the points, the edge lists and the cameras: as uvo_ba_problem */
+  const uint8_t* point_bad;        /* may be NULL */
+  const int32_t* point_edge_begin;
+  const int32_t* edge_kf;
+  const float* edge_obs;
+  const float* edge_inv_sigma2;
+  const int32_t* edge_camera;
+  const float* cameras;            /* [n_cameras][4], 1..64 rows */
+  double Rbc[9], Pbc[3], gw[3];
+  double gyr_bias_rw2, acc_bias_rw2;
+  const uvo_nav_ba_link* links;    /* [n_links] 0..48 */
+  const uvo_nav_ba_depth* depth;   /* [n_depth] */
+} uvo_nav_ba_problem;
+
+typedef struct uvo_nav_ba_result {
+  uvo_nav_state* kf_state; /* [n_keyframes] P V R of the PVR estimate, dbg dba of the bias estimate; a fixed one's is its input; may be NULL */
+  float* kf_Tcw;           /* [n_keyframes][16] UpdatePoseFromNS; may be NULL */
+  double* point_estimate;  /* [n_points][3]; may be NULL */
+  float* points;           /* [n_points][3]; may be NULL */
+  uint8_t* excluded;       /* [n_edges] 1 where the first check puts the edge at level 1; may be NULL */
+  uint8_t* erased;         /* [n_edges] 1 where the final check erases the observation; may be NULL */
+  int32_t n_excluded, n_erased;
+  int32_t iterations[2];
+  int32_t n_trials, n_syncs;
+} uvo_nav_ba_result;
+
+/* test tap: one record per linearisation (n_edges counts the inertial edges too), uvo_pose_trace_trial records per trial */
+typedef struct uvo_nav_ba_trace_lin {
+  int32_t round, iteration;
+  int32_t n_edges, n_free, n_points, pad_;
+  double chi2;
+  double maxdiag;
+} uvo_nav_ba_trace_lin;
+typedef struct uvo_nav_ba_trace {
+  int32_t n_lin, n_trials;
+  uvo_nav_ba_trace_lin lin[32];
+  uvo_pose_trace_trial trial[320];
+} uvo_nav_ba_trace;
+
+/* max_free 1..24 (a 360 x 360 solve), max_fixed 0..256, max_points 1..32768, max_edges 1..262144, max_depth 0..256 (UVO_E_BADARG
+ * otherwise).  The adjuster lives on a uvo_matcher handle, as uvo_bundle_adjuster, and must be destroyed before it. */
+int uvo_nav_bundle_adjuster_create(uvo_matcher* m, int max_free, int max_fixed, int max_points, int max_edges, int max_depth,
+                                   uvo_nav_bundle_adjuster** out);
+void uvo_nav_bundle_adjuster_destroy(uvo_nav_bundle_adjuster* a);
+/* UVO_E_CAPACITY: more free or fixed key frames, points, edges, links or depth entries than the adjuster was sized for.
+ * UVO_E_BADARG: as uvo_bundle_adjust, and: a link or depth entry naming a key frame (or a link) out of range or one key frame twice,
+ * one naming the bias vertex of a key frame that carries none, a free key frame with no link ending in it or without a bias vertex.
+ * Nothing is written on an error.  A problem with no free key frame is answered with the inputs unchanged. */
+int uvo_nav_bundle_adjust(uvo_nav_bundle_adjuster* a, const uvo_nav_ba_problem* problem, uvo_nav_ba_result* result);
+/* test tap: the trace of the adjuster's last call (no record when that call optimised nothing). */
+int uvo_nav_bundle_adjuster_trace(uvo_nav_bundle_adjuster* a, uvo_nav_ba_trace* out);
+
 /*
  * Initializer -- replaces USLAM::Initializer (include/Initializer.h, src/Initializer.cc) as Tracking::Initialize (src/Tracking.cc:1340)
  * and the recovery path (:1582) use it: the constructor on the reference frame, then Initialize(current frame, matches) until it

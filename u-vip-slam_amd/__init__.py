@@ -51,6 +51,7 @@ ABI_SYMBOLS = [
     "uvo_sim3solver_query", "uvo_sim3solver_iterate", "uvo_sim3solver_find", "uvo_sim3solver_hypotheses",
     "uvo_sim3_optimizer_create", "uvo_sim3_optimizer_destroy", "uvo_sim3_optimize", "uvo_sim3_optimizer_trace",
     "uvo_bundle_adjuster_create", "uvo_bundle_adjuster_destroy", "uvo_bundle_adjust", "uvo_bundle_adjuster_trace",
+    "uvo_nav_bundle_adjuster_create", "uvo_nav_bundle_adjuster_destroy", "uvo_nav_bundle_adjust", "uvo_nav_bundle_adjuster_trace",
     "uvo_initializer_create", "uvo_initializer_destroy", "uvo_initializer_set_reference", "uvo_initializer_initialize", "uvo_initializer_hypotheses",
     "uvo_kfdb_create", "uvo_kfdb_destroy", "uvo_kfdb_add", "uvo_kfdb_erase", "uvo_kfdb_clear", "uvo_kfdb_set_covisibles", "uvo_kfdb_detect_reloc",
     "uvo_kfdb_detect_loop", "uvo_kfdb_detect_loop_haloc", "uvo_kfdb_last_query", "uvo_kfdb_last_haloc", "uvo_kfdb_state", "uvo_kfdb_size",
@@ -303,6 +304,11 @@ def _load():
     lib.uvo_bundle_adjuster_destroy.restype = None
     lib.uvo_bundle_adjust.argtypes = [vp, vp, vp]
     lib.uvo_bundle_adjuster_trace.argtypes = [vp, vp]
+    lib.uvo_nav_bundle_adjuster_create.argtypes = [vp, ci, ci, ci, ci, ci, vp]
+    lib.uvo_nav_bundle_adjuster_destroy.argtypes = [vp]
+    lib.uvo_nav_bundle_adjuster_destroy.restype = None
+    lib.uvo_nav_bundle_adjust.argtypes = [vp, vp, vp]
+    lib.uvo_nav_bundle_adjuster_trace.argtypes = [vp, vp]
     lib.uvo_sim3solver_set_create.argtypes = [vp, ci, ci, vp]
     lib.uvo_sim3solver_set_destroy.argtypes = [vp]
     lib.uvo_sim3solver_set_destroy.restype = None
@@ -2096,6 +2102,127 @@ class BundleAdjuster:
         if rc:
             raise UvoError(rc, "uvo_bundle_adjuster_trace")
         return BaTrace(c)
+
+
+NAV_STATE_WORDS = 22      # uvo_nav_state: P V q (x y z w) bg ba dbg dba
+NAVBA_LINK_DTYPE = np.dtype([("kf0", "<i4"), ("kf1", "<i4"), ("dT", "<f8"), ("dP", "<f8", 3), ("dV", "<f8", 3), ("dR", "<f8", 9), ("JPg", "<f8", 9),
+                             ("JPa", "<f8", 9), ("JVg", "<f8", 9), ("JVa", "<f8", 9), ("JRg", "<f8", 9), ("cov", "<f8", 81)])
+NAVBA_DEPTH_DTYPE = np.dtype([("ka", "<i4"), ("kb", "<i4"), ("kc", "<i4"), ("link", "<i4"), ("shi", "<f8"), ("meas", "<f8"), ("info", "<f8")])
+
+
+class NavBaProblemC(ctypes.Structure):
+    """uvo_nav_ba_problem."""
+    _fields_ = [("n_keyframes", ctypes.c_int32), ("n_points", ctypes.c_int32), ("n_edges", ctypes.c_int32), ("n_cameras", ctypes.c_int32),
+                ("n_links", ctypes.c_int32), ("n_depth", ctypes.c_int32), ("kf_state", ctypes.c_void_p), ("kf_fixed", ctypes.c_void_p),
+                ("kf_has_bias", ctypes.c_void_p), ("points", ctypes.c_void_p), ("point_bad", ctypes.c_void_p), ("point_edge_begin", ctypes.c_void_p),
+                ("edge_kf", ctypes.c_void_p), ("edge_obs", ctypes.c_void_p), ("edge_inv_sigma2", ctypes.c_void_p), ("edge_camera", ctypes.c_void_p),
+                ("cameras", ctypes.c_void_p), ("Rbc", ctypes.c_double * 9), ("Pbc", ctypes.c_double * 3), ("gw", ctypes.c_double * 3),
+                ("gyr_bias_rw2", ctypes.c_double), ("acc_bias_rw2", ctypes.c_double), ("links", ctypes.c_void_p), ("depth", ctypes.c_void_p)]
+
+
+class NavBaResultC(ctypes.Structure):
+    """uvo_nav_ba_result."""
+    _fields_ = [("kf_state", ctypes.c_void_p), ("kf_Tcw", ctypes.c_void_p), ("point_estimate", ctypes.c_void_p), ("points", ctypes.c_void_p),
+                ("excluded", ctypes.c_void_p), ("erased", ctypes.c_void_p), ("n_excluded", ctypes.c_int32), ("n_erased", ctypes.c_int32),
+                ("iterations", ctypes.c_int32 * 2), ("n_trials", ctypes.c_int32), ("n_syncs", ctypes.c_int32)]
+
+
+class NavBaTraceC(ctypes.Structure):
+    """uvo_nav_ba_trace."""
+    _fields_ = [("n_lin", ctypes.c_int32), ("n_trials", ctypes.c_int32), ("lin", BaTraceLin * 32), ("trial", PoseTraceTrial * 320)]
+
+
+class NavBaTrace(BaTrace):
+    """The test tap of a call: lin (BA_LIN_DTYPE; n_edges counts the inertial edges too), trial (POSE_TRIAL_DTYPE)."""
+
+
+class NavBaResult:
+    """One adjusted window: kf_state float64[K, 22] (P V q bg ba dbg dba), kf_Tcw float32[K, 4, 4], point_estimate float64[P, 3], points
+    float32[P, 3], excluded uint8[E] (the first check's level 1) and erased uint8[E] (the final check), their counts, iterations, n_trials,
+    n_syncs."""
+
+    def __init__(self, c, arrays):
+        self.kf_state, self.kf_Tcw, self.point_estimate, self.points, self.excluded, self.erased = arrays
+        self.n_excluded, self.n_erased, self.iterations = c.n_excluded, c.n_erased, (c.iterations[0], c.iterations[1])
+        self.n_trials, self.n_syncs = c.n_trials, c.n_syncs
+
+
+def navba_marshal(scene):
+    """A scene dict (states [K, 22], fixed [K], has_bias [K], points [P, 3], point_bad [P] or absent, begin [P + 1], edge_kf [E], edge_obs
+    [E, 2], edge_inv_sigma2 [E], edge_camera [E], cameras [C, 4], Rbc [9], Pbc [3], gw [3], gyr_rw2, acc_rw2, links (NAVBA_LINK_DTYPE [L]),
+    depth (NAVBA_DEPTH_DTYPE [D])) -> (NavBaProblemC, NavBaResultC, the result's arrays, what to keep alive)."""
+    f32, f64, i32, u8 = np.float32, np.float64, np.int32, np.uint8
+    st = np.ascontiguousarray(scene["states"], f64).reshape(-1, NAV_STATE_WORDS)
+    fixed = np.ascontiguousarray(scene["fixed"], u8).reshape(-1)
+    hb = np.ascontiguousarray(scene["has_bias"], u8).reshape(-1)
+    pts = np.ascontiguousarray(scene["points"], f32).reshape(-1, 3)
+    bad = None if scene.get("point_bad") is None else np.ascontiguousarray(scene["point_bad"], u8).reshape(-1)
+    begin = np.ascontiguousarray(scene["begin"], i32).reshape(-1)
+    ekf = np.ascontiguousarray(scene["edge_kf"], i32).reshape(-1)
+    obs = np.ascontiguousarray(scene["edge_obs"], f32).reshape(-1, 2)
+    w = np.ascontiguousarray(scene["edge_inv_sigma2"], f32).reshape(-1)
+    ecam = np.ascontiguousarray(scene["edge_camera"], i32).reshape(-1)
+    cams = np.ascontiguousarray(scene["cameras"], f32).reshape(-1, 4)
+    links = np.ascontiguousarray(scene["links"], NAVBA_LINK_DTYPE).reshape(-1)
+    depth = np.ascontiguousarray(scene["depth"], NAVBA_DEPTH_DTYPE).reshape(-1)
+    K, P, E = len(st), len(pts), len(ekf)
+    if len(fixed) != K or len(hb) != K or len(begin) != P + 1 or len(obs) != E or len(w) != E or len(ecam) != E or (bad is not None and len(bad) != P):
+        raise ValueError("the arrays of the problem differ in length")
+    c = NavBaProblemC()
+    c.n_keyframes, c.n_points, c.n_edges, c.n_cameras, c.n_links, c.n_depth = K, P, E, len(cams), len(links), len(depth)
+    c.kf_state, c.kf_fixed, c.kf_has_bias, c.points = st.ctypes.data, fixed.ctypes.data, hb.ctypes.data, pts.ctypes.data
+    c.point_bad = None if bad is None else bad.ctypes.data
+    c.point_edge_begin, c.edge_kf, c.edge_obs, c.edge_inv_sigma2 = begin.ctypes.data, ekf.ctypes.data, obs.ctypes.data, w.ctypes.data
+    c.edge_camera, c.cameras, c.links, c.depth = ecam.ctypes.data, cams.ctypes.data, links.ctypes.data, depth.ctypes.data
+    c.Rbc[:] = [float(v) for v in np.asarray(scene["Rbc"], f64).reshape(9)]
+    c.Pbc[:] = [float(v) for v in np.asarray(scene["Pbc"], f64).reshape(3)]
+    c.gw[:] = [float(v) for v in np.asarray(scene["gw"], f64).reshape(3)]
+    c.gyr_bias_rw2, c.acc_bias_rw2 = float(scene["gyr_rw2"]), float(scene["acc_rw2"])
+    out = [np.zeros((max(K, 1), NAV_STATE_WORDS)), np.zeros((max(K, 1), 4, 4), f32), np.zeros((max(P, 1), 3)), np.zeros((max(P, 1), 3), f32),
+           np.zeros(max(E, 1), u8), np.zeros(max(E, 1), u8)]
+    r = NavBaResultC()
+    r.kf_state, r.kf_Tcw, r.point_estimate, r.points, r.excluded, r.erased = [a.ctypes.data for a in out]
+    arrays = [out[0][:K], out[1][:K], out[2][:P], out[3][:P], out[4][:E], out[5][:E]]
+    return c, r, arrays, (st, fixed, hb, pts, bad, begin, ekf, obs, w, ecam, cams, links, depth, out)
+
+
+class NavBundleAdjuster:
+    """Optimizer::LocalBundleAdjustmentNavState (src/Optimizer.cc:1105-1732) on an ORBmatcher handle, the mapping thread's stream:
+    adjust() runs one window, every phase a launch of its own and the Levenberg decision on the device.  `_api` exists so that the tests
+    can drive another build through this class."""
+
+    def __init__(self, matcher, max_free=24, max_fixed=64, max_points=8192, max_edges=65536, max_depth=64, _api=None):
+        self._api = _api if _api is not None else lib
+        self._matcher = matcher   # the adjuster launches in the handle's stream: keep it alive
+        self._h = ctypes.c_void_p()
+        rc = self._api.uvo_nav_bundle_adjuster_create(matcher._h if matcher is not None else None, max_free, max_fixed, max_points, max_edges, max_depth,
+                                                      ctypes.byref(self._h))
+        if rc:
+            self._h = None
+            raise UvoError(rc, "uvo_nav_bundle_adjuster_create")
+
+    def close(self):
+        if getattr(self, "_h", None) and self._api is not None:
+            self._api.uvo_nav_bundle_adjuster_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def adjust(self, scene):
+        """scene: the dict navba_marshal() describes -> NavBaResult."""
+        c, r, arrays, keep = navba_marshal(scene)
+        rc = self._api.uvo_nav_bundle_adjust(self._h, ctypes.byref(c), ctypes.byref(r))
+        if rc:
+            raise UvoError(rc, "uvo_nav_bundle_adjust")
+        return NavBaResult(r, arrays)
+
+    def trace(self):
+        """Test tap: NavBaTrace of the last adjust() call."""
+        c = NavBaTraceC()
+        rc = self._api.uvo_nav_bundle_adjuster_trace(self._h, ctypes.byref(c))
+        if rc:
+            raise UvoError(rc, "uvo_nav_bundle_adjuster_trace")
+        return NavBaTrace(c)
 
 
 class InitializerResultC(ctypes.Structure):
