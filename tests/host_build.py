@@ -44,12 +44,12 @@ ARTEFACTS = {}
 ARTEFACTS.update({n: _emu(n, SHARED) for n in ("octree_emu", "pyr_tiles_emu", "strip_plan_emu", "blur_plan_emu")})
 ARTEFACTS.update({n: _emu(n, SHARED + HIP, "hipcc") for n in ("geom_emu", "grider_geom_emu")})
 ARTEFACTS.update({n: _emu(n, SHARED + NO_FMA) for n in ("pnp_emu", "pnpsolver_emu", "sim3solver_emu", "initializer_emu", "poseopt_emu",
-                                                        "sim3opt_emu", "ba_emu", "navopt_emu")})
+                                                        "sim3opt_emu", "ba_emu", "navopt_emu", "navba_emu")})
 ARTEFACTS["math_host"] = _emu("math_host", SHARED + NO_FMA, libs=["-lpthread"])
 ARTEFACTS["kfdb_emu"] = _program("kfdb_emu", ["-Wall", "-Werror"])
-ARTEFACTS.update({n + "_main": _program(n, ["-D%s_MAIN" % n.upper()]) for n in ("poseopt_emu", "sim3opt_emu", "ba_emu", "navopt_emu")})
+ARTEFACTS.update({n + "_main": _program(n, ["-D%s_MAIN" % n.upper()]) for n in ("poseopt_emu", "sim3opt_emu", "ba_emu", "navopt_emu", "navba_emu")})
 ARTEFACTS.update({n: _driver(n) for n in ("compat_scenes", "compat_newpoints", "compat_pnp", "compat_pnpsolver", "compat_sim3solver",
-                                          "compat_kfdb", "compat_poseopt", "compat_sim3opt", "compat_ba", "compat_navopt")})
+                                          "compat_kfdb", "compat_poseopt", "compat_sim3opt", "compat_ba", "compat_navopt", "compat_navba")})
 ARTEFACTS["compat_initializer"] = _driver("compat_initializer", CXX11 + ["-Itests/cpp/opencv_decl_stub"])
 ARTEFACTS["compat_driver"] = _driver("compat_driver", [f for f in CXX11 if f != "-Werror"])
 

@@ -37,15 +37,7 @@ IE_WORDS, IE_J, IE_WJ, IE_E, IE_WE, IE_CHI = 562, 0, 270, 540, 549, 558
 MUTATIONS = {"V_COLUMNS": 1, "SCATTER_0_5": 2, "BACKWARD_PREINT": 3, "CHECK_FLOAT": 4, "KEEP_KERNEL": 5, "FLAGGED_KERNEL_OFF": 6, "FINAL_SKIPS_EXCLUDED": 7,
              "ORDER": 8, "BIAS_NO_DT": 9, "TAU_POSES": 10}
 
-# the host artefacts of this feature, declared here (tests/host_build.py stays as it is) and compiled through host_build.compile_artefact
-ARTEFACTS = {"navba_emu": host_build._emu("navba_emu", host_build.SHARED + host_build.NO_FMA),
-             "navba_emu_main": host_build._program("navba_emu", ["-DNAVBA_EMU_MAIN"]),
-             "compat_navba": host_build._driver("compat_navba")}
-
-
-def build(name, extra=(), suffix=""):
-    return host_build.compile_artefact(ARTEFACTS[name], extra, suffix)
-
+build = host_build.build        # "navba_emu", "navba_emu_main" and "compat_navba" are rows of tests/host_build.py's table
 
 # measured by `python tests/navba_checks.py` (seed 1, ORDERS = 4 permutations x 3 solvers, every scene of navba_model.SCENES); DESIGN.md section 4
 SEED, ORDERS, MARGIN = 1, 4, 4

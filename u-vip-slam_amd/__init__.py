@@ -2036,11 +2036,11 @@ class BaResult:
         self.n_trials, self.n_syncs = c.n_trials, c.n_syncs
 
 
-def ba_marshal(scene, mode=UVO_BA_LOCAL, n_iterations=0):
-    """A scene dict (Tcw [K, 12] or [K, 3, 4], fixed [K], points [P, 3], point_bad [P] or absent, begin [P + 1], edge_kf [E],
-    edge_obs [E, 2], edge_inv_sigma2 [E], edge_camera [E], cameras [C, 4]) -> (BaProblemC, BaResultC, the result's arrays, what to keep alive)."""
+def _ba_graph(scene, c, K, also=()):
+    """The lists uvo_ba_problem and uvo_nav_ba_problem name alike (fixed, points, point_bad, begin, the four edge lists, cameras):
+    converted, their lengths checked against K key frames (`also`: further arrays of K entries) and each other, set in c with the counts
+    -> what to keep alive."""
     f32, i32, u8 = np.float32, np.int32, np.uint8
-    T = np.ascontiguousarray(scene["Tcw"], f32).reshape(-1, 12)
     fixed = np.ascontiguousarray(scene["fixed"], u8).reshape(-1)
     pts = np.ascontiguousarray(scene["points"], f32).reshape(-1, 3)
     bad = None if scene.get("point_bad") is None else np.ascontiguousarray(scene["point_bad"], u8).reshape(-1)
@@ -2050,58 +2050,89 @@ def ba_marshal(scene, mode=UVO_BA_LOCAL, n_iterations=0):
     w = np.ascontiguousarray(scene["edge_inv_sigma2"], f32).reshape(-1)
     ecam = np.ascontiguousarray(scene["edge_camera"], i32).reshape(-1)
     cams = np.ascontiguousarray(scene["cameras"], f32).reshape(-1, 4)
-    K, P, E = len(T), len(pts), len(ekf)
-    if len(fixed) != K or len(begin) != P + 1 or len(obs) != E or len(w) != E or len(ecam) != E or (bad is not None and len(bad) != P):
+    P, E = len(pts), len(ekf)
+    if any(len(a) != K for a in (fixed,) + tuple(also)) or len(begin) != P + 1 or len(obs) != E or len(w) != E or len(ecam) != E or (bad is not None and len(bad) != P):
         raise ValueError("the arrays of the problem differ in length")
-    c = BaProblemC()
-    c.mode, c.n_iterations, c.n_keyframes, c.n_points, c.n_edges, c.n_cameras = mode, n_iterations, K, P, E, len(cams)
-    c.kf_Tcw, c.kf_fixed, c.points, c.point_bad = T.ctypes.data, fixed.ctypes.data, pts.ctypes.data, None if bad is None else bad.ctypes.data
+    c.n_keyframes, c.n_points, c.n_edges, c.n_cameras = K, P, E, len(cams)
+    c.kf_fixed, c.points, c.point_bad = fixed.ctypes.data, pts.ctypes.data, None if bad is None else bad.ctypes.data
     c.point_edge_begin, c.edge_kf, c.edge_obs, c.edge_inv_sigma2 = begin.ctypes.data, ekf.ctypes.data, obs.ctypes.data, w.ctypes.data
     c.edge_camera, c.cameras = ecam.ctypes.data, cams.ctypes.data
-    out = [np.zeros((max(K, 1), 7)), np.zeros((max(K, 1), 4, 4), f32), np.zeros((max(P, 1), 3)), np.zeros((max(P, 1), 3), f32),
-           np.zeros(max(E, 1), u8), np.zeros(max(E, 1), u8)]
+    return fixed, pts, bad, begin, ekf, obs, w, ecam, cams
+
+
+def _ba_outputs(c, r, kf_words, names):
+    """The six arrays of a result of problem c, the key frames' estimates kf_words wide, set in r under `names` -> (the arrays cut to
+    the problem's counts, what to keep alive)."""
+    K, P, E = c.n_keyframes, c.n_points, c.n_edges
+    out = [np.zeros((max(K, 1), kf_words)), np.zeros((max(K, 1), 4, 4), np.float32), np.zeros((max(P, 1), 3)), np.zeros((max(P, 1), 3), np.float32),
+           np.zeros(max(E, 1), np.uint8), np.zeros(max(E, 1), np.uint8)]
+    for name, a in zip(names, out):
+        setattr(r, name, a.ctypes.data)
+    return [out[0][:K], out[1][:K], out[2][:P], out[3][:P], out[4][:E], out[5][:E]], out
+
+
+def ba_marshal(scene, mode=UVO_BA_LOCAL, n_iterations=0):
+    """A scene dict (Tcw [K, 12] or [K, 3, 4], fixed [K], points [P, 3], point_bad [P] or absent, begin [P + 1], edge_kf [E],
+    edge_obs [E, 2], edge_inv_sigma2 [E], edge_camera [E], cameras [C, 4]) -> (BaProblemC, BaResultC, the result's arrays, what to keep alive)."""
+    T = np.ascontiguousarray(scene["Tcw"], np.float32).reshape(-1, 12)
+    c = BaProblemC()
+    graph = _ba_graph(scene, c, len(T))
+    c.mode, c.n_iterations, c.kf_Tcw = mode, n_iterations, T.ctypes.data
     r = BaResultC()
-    r.kf_estimate, r.kf_Tcw, r.point_estimate, r.points, r.removed1, r.removed2 = [a.ctypes.data for a in out]
-    arrays = [out[0][:K], out[1][:K], out[2][:P], out[3][:P], out[4][:E], out[5][:E]]
-    return c, r, arrays, (T, fixed, pts, bad, begin, ekf, obs, w, ecam, cams, out)
+    arrays, out = _ba_outputs(c, r, 7, ("kf_estimate", "kf_Tcw", "point_estimate", "points", "removed1", "removed2"))
+    return c, r, arrays, (T, graph, out)
 
 
-class BundleAdjuster:
-    """Optimizer::LocalBundleAdjustment (src/Optimizer.cc:2147-2405) and Optimizer::BundleAdjustment (:1896-2010) on an ORBmatcher
-    handle, the mapping thread's stream: adjust() runs one problem, every phase a launch of its own and the Levenberg decision on the
-    device.  `_api` exists so that the tests can drive another build through this class."""
+class _Adjuster:
+    """What BundleAdjuster and NavBundleAdjuster share: a handle made by `<_handle>_create` on an ORBmatcher handle, run by `_call`, read
+    by `<_handle>_trace`, freed by `<_handle>_destroy`."""
 
-    def __init__(self, matcher, max_free=32, max_fixed=64, max_points=8192, max_edges=65536, _api=None):
+    def __init__(self, matcher, sizes, _api):
         self._api = _api if _api is not None else lib
         self._matcher = matcher   # the adjuster launches in the handle's stream: keep it alive
         self._h = ctypes.c_void_p()
-        rc = self._api.uvo_bundle_adjuster_create(matcher._h if matcher is not None else None, max_free, max_fixed, max_points, max_edges, ctypes.byref(self._h))
+        rc = getattr(self._api, self._handle + "_create")(matcher._h if matcher is not None else None, *sizes, ctypes.byref(self._h))
         if rc:
             self._h = None
-            raise UvoError(rc, "uvo_bundle_adjuster_create")
+            raise UvoError(rc, self._handle + "_create")
 
     def close(self):
         if getattr(self, "_h", None) and self._api is not None:
-            self._api.uvo_bundle_adjuster_destroy(self._h)
+            getattr(self._api, self._handle + "_destroy")(self._h)
             self._h = None
 
     __del__ = close
 
+    def _adjust(self, c, r):
+        rc = getattr(self._api, self._call)(self._h, ctypes.byref(c), ctypes.byref(r))
+        if rc:
+            raise UvoError(rc, self._call)
+
+    def _trace(self, c):
+        rc = getattr(self._api, self._handle + "_trace")(self._h, ctypes.byref(c))
+        if rc:
+            raise UvoError(rc, self._handle + "_trace")
+        return c
+
+
+class BundleAdjuster(_Adjuster):
+    """Optimizer::LocalBundleAdjustment (src/Optimizer.cc:2147-2405) and Optimizer::BundleAdjustment (:1896-2010) on an ORBmatcher
+    handle, the mapping thread's stream: adjust() runs one problem, every phase a launch of its own and the Levenberg decision on the
+    device.  `_api` exists so that the tests can drive another build through this class."""
+    _handle, _call = "uvo_bundle_adjuster", "uvo_bundle_adjust"
+
+    def __init__(self, matcher, max_free=32, max_fixed=64, max_points=8192, max_edges=65536, _api=None):
+        super().__init__(matcher, (max_free, max_fixed, max_points, max_edges), _api)
+
     def adjust(self, scene, mode=UVO_BA_LOCAL, n_iterations=0):
         """scene: the dict ba_marshal() describes -> BaResult."""
         c, r, arrays, keep = ba_marshal(scene, mode, n_iterations)
-        rc = self._api.uvo_bundle_adjust(self._h, ctypes.byref(c), ctypes.byref(r))
-        if rc:
-            raise UvoError(rc, "uvo_bundle_adjust")
+        self._adjust(c, r)
         return BaResult(r, arrays)
 
     def trace(self):
         """Test tap: BaTrace of the last adjust() call."""
-        c = BaTraceC()
-        rc = self._api.uvo_bundle_adjuster_trace(self._h, ctypes.byref(c))
-        if rc:
-            raise UvoError(rc, "uvo_bundle_adjuster_trace")
-        return BaTrace(c)
+        return BaTrace(self._trace(BaTraceC()))
 
 
 NAV_STATE_WORDS = 22      # uvo_nav_state: P V q (x y z w) bg ba dbg dba
@@ -2151,78 +2182,42 @@ def navba_marshal(scene):
     """A scene dict (states [K, 22], fixed [K], has_bias [K], points [P, 3], point_bad [P] or absent, begin [P + 1], edge_kf [E], edge_obs
     [E, 2], edge_inv_sigma2 [E], edge_camera [E], cameras [C, 4], Rbc [9], Pbc [3], gw [3], gyr_rw2, acc_rw2, links (NAVBA_LINK_DTYPE [L]),
     depth (NAVBA_DEPTH_DTYPE [D])) -> (NavBaProblemC, NavBaResultC, the result's arrays, what to keep alive)."""
-    f32, f64, i32, u8 = np.float32, np.float64, np.int32, np.uint8
+    f64 = np.float64
     st = np.ascontiguousarray(scene["states"], f64).reshape(-1, NAV_STATE_WORDS)
-    fixed = np.ascontiguousarray(scene["fixed"], u8).reshape(-1)
-    hb = np.ascontiguousarray(scene["has_bias"], u8).reshape(-1)
-    pts = np.ascontiguousarray(scene["points"], f32).reshape(-1, 3)
-    bad = None if scene.get("point_bad") is None else np.ascontiguousarray(scene["point_bad"], u8).reshape(-1)
-    begin = np.ascontiguousarray(scene["begin"], i32).reshape(-1)
-    ekf = np.ascontiguousarray(scene["edge_kf"], i32).reshape(-1)
-    obs = np.ascontiguousarray(scene["edge_obs"], f32).reshape(-1, 2)
-    w = np.ascontiguousarray(scene["edge_inv_sigma2"], f32).reshape(-1)
-    ecam = np.ascontiguousarray(scene["edge_camera"], i32).reshape(-1)
-    cams = np.ascontiguousarray(scene["cameras"], f32).reshape(-1, 4)
+    hb = np.ascontiguousarray(scene["has_bias"], np.uint8).reshape(-1)
     links = np.ascontiguousarray(scene["links"], NAVBA_LINK_DTYPE).reshape(-1)
     depth = np.ascontiguousarray(scene["depth"], NAVBA_DEPTH_DTYPE).reshape(-1)
-    K, P, E = len(st), len(pts), len(ekf)
-    if len(fixed) != K or len(hb) != K or len(begin) != P + 1 or len(obs) != E or len(w) != E or len(ecam) != E or (bad is not None and len(bad) != P):
-        raise ValueError("the arrays of the problem differ in length")
     c = NavBaProblemC()
-    c.n_keyframes, c.n_points, c.n_edges, c.n_cameras, c.n_links, c.n_depth = K, P, E, len(cams), len(links), len(depth)
-    c.kf_state, c.kf_fixed, c.kf_has_bias, c.points = st.ctypes.data, fixed.ctypes.data, hb.ctypes.data, pts.ctypes.data
-    c.point_bad = None if bad is None else bad.ctypes.data
-    c.point_edge_begin, c.edge_kf, c.edge_obs, c.edge_inv_sigma2 = begin.ctypes.data, ekf.ctypes.data, obs.ctypes.data, w.ctypes.data
-    c.edge_camera, c.cameras, c.links, c.depth = ecam.ctypes.data, cams.ctypes.data, links.ctypes.data, depth.ctypes.data
+    graph = _ba_graph(scene, c, len(st), also=(hb,))
+    c.n_links, c.n_depth = len(links), len(depth)
+    c.kf_state, c.kf_has_bias, c.links, c.depth = st.ctypes.data, hb.ctypes.data, links.ctypes.data, depth.ctypes.data
     c.Rbc[:] = [float(v) for v in np.asarray(scene["Rbc"], f64).reshape(9)]
     c.Pbc[:] = [float(v) for v in np.asarray(scene["Pbc"], f64).reshape(3)]
     c.gw[:] = [float(v) for v in np.asarray(scene["gw"], f64).reshape(3)]
     c.gyr_bias_rw2, c.acc_bias_rw2 = float(scene["gyr_rw2"]), float(scene["acc_rw2"])
-    out = [np.zeros((max(K, 1), NAV_STATE_WORDS)), np.zeros((max(K, 1), 4, 4), f32), np.zeros((max(P, 1), 3)), np.zeros((max(P, 1), 3), f32),
-           np.zeros(max(E, 1), u8), np.zeros(max(E, 1), u8)]
     r = NavBaResultC()
-    r.kf_state, r.kf_Tcw, r.point_estimate, r.points, r.excluded, r.erased = [a.ctypes.data for a in out]
-    arrays = [out[0][:K], out[1][:K], out[2][:P], out[3][:P], out[4][:E], out[5][:E]]
-    return c, r, arrays, (st, fixed, hb, pts, bad, begin, ekf, obs, w, ecam, cams, links, depth, out)
+    arrays, out = _ba_outputs(c, r, NAV_STATE_WORDS, ("kf_state", "kf_Tcw", "point_estimate", "points", "excluded", "erased"))
+    return c, r, arrays, (st, hb, links, depth, graph, out)
 
 
-class NavBundleAdjuster:
+class NavBundleAdjuster(_Adjuster):
     """Optimizer::LocalBundleAdjustmentNavState (src/Optimizer.cc:1105-1732) on an ORBmatcher handle, the mapping thread's stream:
     adjust() runs one window, every phase a launch of its own and the Levenberg decision on the device.  `_api` exists so that the tests
     can drive another build through this class."""
+    _handle, _call = "uvo_nav_bundle_adjuster", "uvo_nav_bundle_adjust"
 
     def __init__(self, matcher, max_free=24, max_fixed=64, max_points=8192, max_edges=65536, max_depth=64, _api=None):
-        self._api = _api if _api is not None else lib
-        self._matcher = matcher   # the adjuster launches in the handle's stream: keep it alive
-        self._h = ctypes.c_void_p()
-        rc = self._api.uvo_nav_bundle_adjuster_create(matcher._h if matcher is not None else None, max_free, max_fixed, max_points, max_edges, max_depth,
-                                                      ctypes.byref(self._h))
-        if rc:
-            self._h = None
-            raise UvoError(rc, "uvo_nav_bundle_adjuster_create")
-
-    def close(self):
-        if getattr(self, "_h", None) and self._api is not None:
-            self._api.uvo_nav_bundle_adjuster_destroy(self._h)
-            self._h = None
-
-    __del__ = close
+        super().__init__(matcher, (max_free, max_fixed, max_points, max_edges, max_depth), _api)
 
     def adjust(self, scene):
         """scene: the dict navba_marshal() describes -> NavBaResult."""
         c, r, arrays, keep = navba_marshal(scene)
-        rc = self._api.uvo_nav_bundle_adjust(self._h, ctypes.byref(c), ctypes.byref(r))
-        if rc:
-            raise UvoError(rc, "uvo_nav_bundle_adjust")
+        self._adjust(c, r)
         return NavBaResult(r, arrays)
 
     def trace(self):
         """Test tap: NavBaTrace of the last adjust() call."""
-        c = NavBaTraceC()
-        rc = self._api.uvo_nav_bundle_adjuster_trace(self._h, ctypes.byref(c))
-        if rc:
-            raise UvoError(rc, "uvo_nav_bundle_adjuster_trace")
-        return NavBaTrace(c)
+        return NavBaTrace(self._trace(NavBaTraceC()))
 
 
 class InitializerResultC(ctypes.Structure):

@@ -22,6 +22,8 @@
 //   5. the reduced system: a dense unpivoted LDL^T in natural key-frame order, in place on the lower triangle; every entry receives its
 //      updates in ascending k as v - (L_ik * L_jk) * d_k; forward substitution in ascending k, back substitution in descending k.
 // No floating-point atomics.  The largest diagonal entry is a maximum: any order; a NaN entry makes it NaN.
+// These shapes are also navba_core.hpp's, over its own key-frame unknowns.  What both cores run is written once, in the section "the
+// Schur pieces" below, templated on the workspace; this file owns it, navba_core.hpp calls it.
 //
 // Departures from the reference, stated in uvo.h and DESIGN.md section 4: the dense LDL^T in place of SimplicialLDLT under an AMD
 // ordering ("ok" = every pivot finite and > 0); the sums' shapes above in place of g2o's serial order over its own edge and vertex
@@ -176,6 +178,256 @@ PO_HD int free_of(const Ws& W, int e) {
   return f;
 }
 
+// ---- the Schur pieces ------------------------------------------------------------------------------------------------------------------
+// What does not depend on what a key frame's unknowns are, stated once for this core and navba_core.hpp: WS is either core's
+// workspace, whose fields of one name have one meaning.  A mono edge's pose Jacobian is 2 x 6 in both.  No mutation lives in here: a
+// core's switches stay at its call sites.
+
+// shape 1: Hll's 6 entries and b_l of point j into H, stored with p_on.  Returns whether the point has an active edge.
+template <class WS>
+PO_HD bool point_sum(const WS& W, int j, double H[9]) {
+  SIM3_UNROLL
+  for (int k = 0; k < 9; ++k) H[k] = 0.;
+  int on = 0;
+  PO_NOUNROLL
+  for (int e = W.pt_begin[j]; e < W.pt_begin[j + 1]; ++e) {
+    if (W.e_off[e]) continue;
+    on = 1;
+    const double* L = W.e_lin + (size_t)e * kEdgeWords;
+    int k = 0;
+    SIM3_UNROLL
+    for (int a = 0; a < 3; ++a)
+      SIM3_UNROLL
+      for (int b = a; b < 3; ++b, ++k) H[k] = H[k] + ((L[12 + a] * L[18]) * L[12 + b] + (L[15 + a] * L[18]) * L[15 + b]);
+    SIM3_UNROLL
+    for (int a = 0; a < 3; ++a) H[6 + a] = H[6 + a] + (L[12 + a] * L[19] + L[15 + a] * L[20]);
+  }
+  SIM3_UNROLL
+  for (int k = 0; k < 9; ++k) W.Hll[9 * (size_t)j + k] = H[k];
+  W.p_on[j] = (uint8_t)on;
+  return on != 0;
+}
+PO_HD double point_maxdiag(const double H[9]) { return max_nan(max_nan(fabs(H[0]), fabs(H[3])), fabs(H[5])); }
+
+// shape 2, lane l's share: entries l, l + 256, ... of the n edges listed from kl_edge[b0] onto the 21 + 6 sums
+template <class WS>
+PO_HD void kf_accumulate(const WS& W, int b0, int n, int l, double* acc) {
+  PO_NOUNROLL
+  for (int i = l; i < n; i += kLanes) {
+    const int e = W.kl_edge[b0 + i];
+    if (W.e_off[e]) continue;
+    const double* L = W.e_lin + (size_t)e * kEdgeWords;
+    int k = 0;
+    SIM3_UNROLL
+    for (int a = 0; a < 6; ++a)
+      SIM3_UNROLL
+      for (int b = a; b < 6; ++b, ++k) acc[k] = acc[k] + ((L[a] * L[18]) * L[b] + (L[6 + a] * L[18]) * L[6 + b]);
+    SIM3_UNROLL
+    for (int a = 0; a < 6; ++a) acc[21 + a] = acc[21 + a] + (L[a] * L[19] + L[6 + a] * L[20]);
+  }
+}
+
+// Dinv = (Hll + lambda I)^-1 as the adjugate over the determinant, written out as Eigen's fixed-size inverse() is; Dinv b_l
+template <class WS>
+PO_HD void point_dinv(const WS& W, int j, double lambda) {
+  const double* H = W.Hll + 9 * (size_t)j;
+  const double m00 = H[0] + lambda, m01 = H[1], m02 = H[2], m11 = H[3] + lambda, m12 = H[4], m22 = H[5] + lambda;
+  const double c00 = m11 * m22 - m12 * m12, c01 = m12 * m02 - m01 * m22, c02 = m01 * m12 - m11 * m02;
+  const double c11 = m00 * m22 - m02 * m02, c12 = m01 * m02 - m00 * m12, c22 = m00 * m11 - m01 * m01;
+  const double det = (m00 * c00 + m01 * c01) + m02 * c02;
+  const double inv = 1. / det;
+  double* D = W.Dinv + 9 * (size_t)j;
+  D[0] = c00 * inv, D[1] = c01 * inv, D[2] = c02 * inv, D[3] = c11 * inv, D[4] = c12 * inv, D[5] = c22 * inv;
+  D[6] = (D[0] * H[6] + D[1] * H[7]) + D[2] * H[8];
+  D[7] = (D[1] * H[6] + D[3] * H[7]) + D[4] * H[8];
+  D[8] = (D[2] * H[6] + D[4] * H[7]) + D[5] * H[8];
+}
+
+// Schur block blk is (i1, i2), i1 <= i2, in the order (0,0) (0,1) .. (0,F-1) (1,1) ..
+PO_HD void block_of(int blk, int F, int* i1, int* i2) {
+  int i = 0, rest = blk;
+  while (rest >= F - i) rest -= F - i, ++i;
+  *i1 = i, *i2 = i + rest;
+}
+
+PO_HD int tri6(int a, int b) {  // index of (a, b), a <= b, among the 21 upper entries
+  int idx = 0;
+  for (int r = 0; r < a; ++r) idx += 6 - r;
+  return idx + (b - a);
+}
+
+// shape 3, lane l's share of block (i1, i2): the 36 sums of W_i1j Dinv_j W_i2j^T and, in a diagonal block, the 6 of W_i1j Dinv_j b_lj
+template <class WS>
+PO_HD void schur_accumulate(const WS& W, int i1, int i2, int l, double* acc) {
+  const int b0 = W.kl_begin[i1], n = W.kl_begin[i1 + 1] - b0;
+  const bool diag = i1 == i2;
+  PO_NOUNROLL
+  for (int i = l; i < n; i += kLanes) {
+    const int e1 = W.kl_edge[b0 + i];
+    if (W.e_off[e1]) continue;
+    const int j = W.e_pt[e1];
+    const int e2 = diag ? e1 : W.fp_edge[(size_t)i2 * W.P + j];
+    if (e2 < 0 || W.e_off[e2]) continue;
+    const double* D = W.Dinv + 9 * (size_t)j;
+    double W1[18], Y[18];
+    edge_W(W.e_lin + (size_t)e1 * kEdgeWords, W1);
+    SIM3_UNROLL
+    for (int a = 0; a < 6; ++a) {
+      const double w0 = W1[a * 3], w1 = W1[a * 3 + 1], w2 = W1[a * 3 + 2];
+      Y[a * 3] = (w0 * D[0] + w1 * D[1]) + w2 * D[2];
+      Y[a * 3 + 1] = (w0 * D[1] + w1 * D[3]) + w2 * D[4];
+      Y[a * 3 + 2] = (w0 * D[2] + w1 * D[4]) + w2 * D[5];
+      if (diag) acc[36 + a] = acc[36 + a] + ((w0 * D[6] + w1 * D[7]) + w2 * D[8]);
+    }
+    double W2[18];
+    edge_W(W.e_lin + (size_t)e2 * kEdgeWords, W2);
+    SIM3_UNROLL
+    for (int a = 0; a < 6; ++a)
+      SIM3_UNROLL
+      for (int b = 0; b < 6; ++b) acc[a * 6 + b] = acc[a * 6 + b] + ((Y[a * 3] * W2[b * 3] + Y[a * 3 + 1] * W2[b * 3 + 1]) + Y[a * 3 + 2] * W2[b * 3 + 2]);
+  }
+}
+
+// shape 5: A x = b for the N x N system whose lower triangle is A, factorised in place; col and y are the team's two vectors of N words.
+// Returns whether every pivot was finite and > 0; y holds x (whatever the pivots were).
+template <class Team>
+PO_HD bool ldlt_solve(Team& T, double* A, int N, const double* b, double* col, double* y) {
+  bool ok = true;
+  T.par(N, [&](int i) { y[i] = b[i]; });
+  PO_NOUNROLL
+  for (int k = 0; k < N; ++k) {
+    const double dk = A[(size_t)k * N + k];
+    ok = ok && dk > 0. && dk <= DBL_MAX;
+    T.par(N - k - 1, [&](int r) {
+      const int i = k + 1 + r;
+      const double v = A[(size_t)i * N + k] / dk;
+      A[(size_t)i * N + k] = v, col[i] = v;
+    });
+    T.par2(N - k - 1, N - k - 1, [&](int r, int c) {
+      if (c > r) return;
+      const int i = k + 1 + r, j = k + 1 + c;
+      A[(size_t)i * N + j] = A[(size_t)i * N + j] - (col[i] * col[j]) * dk;
+    });
+  }
+  PO_NOUNROLL
+  for (int k = 0; k < N; ++k) {
+    const double yk = y[k];
+    T.par(N - k - 1, [&](int r) {
+      const int i = k + 1 + r;
+      y[i] = y[i] - A[(size_t)i * N + k] * yk;
+    });
+  }
+  T.par(N, [&](int i) { y[i] = y[i] / A[(size_t)i * N + i]; });
+  PO_NOUNROLL
+  for (int k = N - 1; k >= 1; --k) {
+    const double xk = y[k];
+    T.par(k, [&](int i) { y[i] = y[i] - A[(size_t)k * N + i] * xk; });
+  }
+  return ok;
+}
+
+// Point j of the system: x_l = Dinv (b_l - W^T x_p) when the solve succeeded (else x_l keeps its value), X_try = X + x_l.  Returns the
+// point's share of x . (lambda x + b).  step6(e, x) says whether edge e reaches a free key frame of the system and, if so, gives the six
+// entries of x_p that belong to the edge's (dP, dPhi) or pose columns.
+template <class WS, class Step6>
+PO_HD double point_step(const WS& W, int j, bool ok, double lambda, Step6 step6) {
+  double* xl = W.xl + 3 * (size_t)j;
+  const double* H = W.Hll + 9 * (size_t)j;
+  if (ok) {
+    double c[3] = {H[6], H[7], H[8]};
+    PO_NOUNROLL
+    for (int e = W.pt_begin[j]; e < W.pt_begin[j + 1]; ++e) {
+      if (W.e_off[e]) continue;
+      double x[6];
+      if (!step6(e, x)) continue;
+      double Wm[18];
+      edge_W(W.e_lin + (size_t)e * kEdgeWords, Wm);
+      SIM3_UNROLL
+      for (int b = 0; b < 3; ++b) {
+        double t = Wm[b] * -x[0];
+        SIM3_UNROLL
+        for (int a = 1; a < 6; ++a) t = t + Wm[a * 3 + b] * -x[a];
+        c[b] = c[b] + t;
+      }
+    }
+    const double* D = W.Dinv + 9 * (size_t)j;
+    xl[0] = (D[0] * c[0] + D[1] * c[1]) + D[2] * c[2];
+    xl[1] = (D[1] * c[0] + D[3] * c[1]) + D[4] * c[2];
+    xl[2] = (D[2] * c[0] + D[4] * c[1]) + D[5] * c[2];
+  }
+  double t = 0.;
+  SIM3_UNROLL
+  for (int b = 0; b < 3; ++b) {
+    W.X_try[3 * (size_t)j + b] = W.X[3 * (size_t)j + b] + xl[b];
+    t = t + xl[b] * (lambda * xl[b] + H[6 + b]);
+  }
+  return t;
+}
+
+// ---- the Levenberg driver's control block: the lead lane's parts of init, lin_ctl and trial_ctl -------------------------------------------
+template <class WS>
+PO_HD void ctl_reset(const WS& W) {
+  Ctl& c = *W.ctl;
+  c.lambda = 0., c.ni = 2., c.cur = 0., c.ini = 0., c.rho = 0.;
+  c.round = -1, c.it = 0, c.q = 0, c.stalled = 0, c.status = 0, c.solve_ok = 0, c.n_lin = 0, c.n_trials = 0;
+  c.its[0] = c.its[1] = 0;
+  W.trace->n_lin = 0, W.trace->n_trials = 0;
+}
+
+// a linearisation with chi2 `chi` and largest diagonal entry `mx`: computeLambdaInit at the first iteration of an optimize(), the
+// trace record, and on to the trials
+template <class WS>
+PO_HD void levenberg_linearised(const WS& W, double chi, double mx, int n_edges, int n_free, int n_points) {
+  Ctl& c = *W.ctl;
+  c.cur = chi, c.ini = chi;
+  if (c.it == 0) c.lambda = 1e-5 * mx, c.ni = 2., c.stalled = 0;
+  c.q = 0, c.rho = 0.;
+  if (c.n_lin < kMaxLin) {
+    TraceLin& r = W.trace->lin[c.n_lin];
+    r.round = c.round, r.iteration = c.it, r.n_edges = n_edges, r.n_free = n_free, r.n_points = n_points, r.pad_ = 0;
+    r.chi2 = chi, r.maxdiag = mx;
+  }
+  c.n_lin = c.n_lin + 1;
+  W.trace->n_lin = c.n_lin;
+  c.its[c.round] = c.its[c.round] + 1;
+  c.status = kStTrial;
+}
+
+// a trial that started from (lambda, cur) and gave (ok, tmp, scale, rho): the trace record, lambda and ni, and what comes next
+template <class WS>
+PO_HD void levenberg_decide(const WS& W, double lambda, double cur, bool ok, double tmp, double scale, double rho, bool accept) {
+  Ctl& c = *W.ctl;
+  if (c.n_trials < kMaxTrialRecs) {
+    poseopt::TraceTrial& r = W.trace->trial[c.n_trials];
+    r.lin = c.n_lin - 1, r.ok = ok ? 1 : 0, r.accepted = accept ? 1 : 0, r.pad_ = 0;
+    r.lambda = lambda, r.cur = cur, r.tmp = tmp, r.scale = scale;
+  }
+  c.n_trials = c.n_trials + 1;
+  W.trace->n_trials = c.n_trials;
+  double ni = c.ni, lam = lambda, now = cur;
+  if (accept) {
+    const double u = 2. * rho - 1.;
+    double alpha = 1. - u * u * u;
+    alpha = 2. / 3. < alpha ? 2. / 3. : alpha;
+    const double sf = 1. / 3. < alpha ? alpha : 1. / 3.;
+    lam = lam * sf, ni = 2., now = tmp;
+  } else {
+    lam = lam * ni, ni = ni * 2.;
+  }
+  const int q = c.q + 1;
+  c.lambda = lam, c.ni = ni, c.cur = now, c.rho = rho, c.q = q;
+  if (rho < 0. && q < kMaxTrials) {
+    c.status = kStTrial;
+  } else if (q == kMaxTrials || rho == 0.) {  // Terminate
+    c.status = kStStop;
+  } else {
+    if ((c.ini - now) * 1e3 < c.ini) c.stalled = c.stalled + 1;
+    else c.stalled = 0;
+    c.status = c.stalled >= 3 ? kStStop : kStLinearise;
+    c.it = c.it + 1;
+  }
+}
+
 // ---- phases --------------------------------------------------------------------------------------------------------------------------
 template <int MUT, class Team>
 PO_HD void phase_init(const Ws& W, Team& T, int blk) {
@@ -194,13 +446,7 @@ PO_HD void phase_init(const Ws& W, Team& T, int blk) {
       for (int k = 0; k < 3; ++k) W.X[3 * (size_t)i + k] = W.X_try[3 * (size_t)i + k] = (double)W.pts[3 * (size_t)i + k];
     }
     if (i < W.E) W.e_off[i] = 0, W.e_chi2[i] = 0., W.removed1[i] = 0, W.removed2[i] = 0;
-    if (i == 0) {
-      Ctl& c = *W.ctl;
-      c.lambda = 0., c.ni = 2., c.cur = 0., c.ini = 0., c.rho = 0.;
-      c.round = -1, c.it = 0, c.q = 0, c.stalled = 0, c.status = 0, c.solve_ok = 0, c.n_lin = 0, c.n_trials = 0;
-      c.its[0] = c.its[1] = 0;
-      W.trace->n_lin = 0, W.trace->n_trials = 0;
-    }
+    if (i == 0) ctl_reset(W);
   });
 }
 
@@ -239,26 +485,10 @@ PO_HD void phase_point_sum(const Ws& W, Team& T, int blk) {
   const double mx = T.maxr([&](int l) {
     const int j = blk * kLanes + l;
     if (j >= W.P) return 0.;
-    double H[9] = {0., 0., 0., 0., 0., 0., 0., 0., 0.};
-    int on = 0;
-    PO_NOUNROLL
-    for (int e = W.pt_begin[j]; e < W.pt_begin[j + 1]; ++e) {
-      if (W.e_off[e]) continue;
-      on = 1;
-      const double* L = W.e_lin + (size_t)e * kEdgeWords;
-      int k = 0;
-      SIM3_UNROLL
-      for (int a = 0; a < 3; ++a)
-        SIM3_UNROLL
-        for (int b = a; b < 3; ++b, ++k) H[k] = H[k] + ((L[12 + a] * L[18]) * L[12 + b] + (L[15 + a] * L[18]) * L[15 + b]);
-      SIM3_UNROLL
-      for (int a = 0; a < 3; ++a) H[6 + a] = H[6 + a] + (L[12 + a] * L[19] + L[15 + a] * L[20]);
-    }
-    SIM3_UNROLL
-    for (int k = 0; k < 9; ++k) W.Hll[9 * (size_t)j + k] = H[k];
-    W.p_on[j] = (uint8_t)on;
+    double H[9];
+    point_sum(W, j, H);
     if (MUT == kMutTauPoses) return 0.;
-    return max_nan(max_nan(fabs(H[0]), fabs(H[3])), fabs(H[5]));
+    return point_maxdiag(H);
   });
   if (T.lead()) W.chunk_max[blk] = mx;
 }
@@ -267,23 +497,7 @@ template <int MUT, class Team>
 PO_HD void phase_kf_sum(const Ws& W, Team& T, int f) {
   const int b0 = W.kl_begin[f], n = W.kl_begin[f + 1] - b0;
   double S[27];
-  T.template sum<27>(
-      [&](int l, double* acc) {
-        PO_NOUNROLL
-        for (int i = l; i < n; i += kLanes) {
-          const int e = W.kl_edge[b0 + i];
-          if (W.e_off[e]) continue;
-          const double* L = W.e_lin + (size_t)e * kEdgeWords;
-          int k = 0;
-          SIM3_UNROLL
-          for (int a = 0; a < 6; ++a)
-            SIM3_UNROLL
-            for (int b = a; b < 6; ++b, ++k) acc[k] = acc[k] + ((L[a] * L[18]) * L[b] + (L[6 + a] * L[18]) * L[6 + b]);
-          SIM3_UNROLL
-          for (int a = 0; a < 6; ++a) acc[21 + a] = acc[21 + a] + (L[a] * L[19] + L[6 + a] * L[20]);
-        }
-      },
-      S);
+  T.template sum<27>([&](int l, double* acc) { kf_accumulate(W, b0, n, l, acc); }, S);
   const int on = T.count([&](int l) {
     int c = 0;
     for (int i = l; i < n; i += kLanes) c += W.e_off[W.kl_edge[b0 + i]] ? 0 : 1;
@@ -328,47 +542,19 @@ PO_HD void phase_lin_ctl(const Ws& W, Team& T, int) {
       double chi = 0.;
       PO_NOUNROLL
       for (int i = 0; i < ce; ++i) chi = chi + W.chunk_chi2[i];
-      c.cur = chi, c.ini = chi;
-      if (c.it == 0) c.lambda = 1e-5 * mx, c.ni = 2., c.stalled = 0;
-      c.q = 0, c.rho = 0.;
       int nf = 0;
       for (int f = 0; f < W.F; ++f) nf += W.f_on[f];
-      if (c.n_lin < kMaxLin) {
-        TraceLin& r = W.trace->lin[c.n_lin];
-        r.round = c.round, r.iteration = c.it, r.n_edges = n_edges, r.n_free = nf, r.n_points = n_points, r.pad_ = 0;
-        r.chi2 = chi, r.maxdiag = mx;
-      }
-      c.n_lin = c.n_lin + 1;
-      W.trace->n_lin = c.n_lin;
-      c.its[c.round] = c.its[c.round] + 1;
-      c.status = kStTrial;
+      levenberg_linearised(W, chi, mx, n_edges, nf, n_points);
     }
   }
 }
 
-// Dinv = (Hll + lambda I)^-1 as the adjugate over the determinant, written out as Eigen's fixed-size inverse() is; Dinv b_l
-template <int MUT>
-PO_HD void point_dinv(const Ws& W, int j, double lambda) {
-  const double* H = W.Hll + 9 * (size_t)j;
-  const double lp = MUT == kMutLambdaPoseOnly || MUT == kMutDinvPlain ? 0. : lambda;
-  const double m00 = H[0] + lp, m01 = H[1], m02 = H[2], m11 = H[3] + lp, m12 = H[4], m22 = H[5] + lp;
-  const double c00 = m11 * m22 - m12 * m12, c01 = m12 * m02 - m01 * m22, c02 = m01 * m12 - m11 * m02;
-  const double c11 = m00 * m22 - m02 * m02, c12 = m01 * m02 - m00 * m12, c22 = m00 * m11 - m01 * m01;
-  const double det = (m00 * c00 + m01 * c01) + m02 * c02;
-  const double inv = 1. / det;
-  double* D = W.Dinv + 9 * (size_t)j;
-  D[0] = c00 * inv, D[1] = c01 * inv, D[2] = c02 * inv, D[3] = c11 * inv, D[4] = c12 * inv, D[5] = c22 * inv;
-  D[6] = (D[0] * H[6] + D[1] * H[7]) + D[2] * H[8];
-  D[7] = (D[1] * H[6] + D[3] * H[7]) + D[4] * H[8];
-  D[8] = (D[2] * H[6] + D[4] * H[7]) + D[5] * H[8];
-}
-
 template <int MUT, class Team>
 PO_HD void phase_dinv(const Ws& W, Team& T, int blk) {
-  const double lambda = W.ctl->lambda;
+  const double lambda = MUT == kMutLambdaPoseOnly || MUT == kMutDinvPlain ? 0. : W.ctl->lambda;
   T.par(kLanes, [&](int l) {
     const int j = blk * kLanes + l;
-    if (j < W.P && W.p_on[j]) point_dinv<MUT>(W, j, lambda);
+    if (j < W.P && W.p_on[j]) point_dinv(W, j, lambda);
   });
 }
 
@@ -376,41 +562,11 @@ PO_HD void phase_dinv(const Ws& W, Team& T, int blk) {
 // the diagonal blocks also give bschur = b_p - sum_j W_ij Dinv_j b_lj
 template <int MUT, class Team>
 PO_HD void phase_schur(const Ws& W, Team& T, int blk) {
-  int i1 = 0, rest = blk;  // blocks in the order (0,0) (0,1) .. (0,F-1) (1,1) ..
-  while (rest >= W.F - i1) rest -= W.F - i1, ++i1;
-  const int i2 = i1 + rest;
-  const int b0 = W.kl_begin[i1], n = W.kl_begin[i1 + 1] - b0;
+  int i1, i2;
+  block_of(blk, W.F, &i1, &i2);
   const bool diag = i1 == i2;
   double* S = T.shared();
-  T.template sum_shared<kSchurSums>(
-      [&](int l, double* acc) {
-        PO_NOUNROLL
-        for (int i = l; i < n; i += kLanes) {
-          const int e1 = W.kl_edge[b0 + i];
-          if (W.e_off[e1]) continue;
-          const int j = W.e_pt[e1];
-          const int e2 = diag ? e1 : W.fp_edge[(size_t)i2 * W.P + j];
-          if (e2 < 0 || W.e_off[e2]) continue;
-          const double* D = W.Dinv + 9 * (size_t)j;
-          double W1[18], Y[18];
-          edge_W(W.e_lin + (size_t)e1 * kEdgeWords, W1);
-          SIM3_UNROLL
-          for (int a = 0; a < 6; ++a) {
-            const double w0 = W1[a * 3], w1 = W1[a * 3 + 1], w2 = W1[a * 3 + 2];
-            Y[a * 3] = (w0 * D[0] + w1 * D[1]) + w2 * D[2];
-            Y[a * 3 + 1] = (w0 * D[1] + w1 * D[3]) + w2 * D[4];
-            Y[a * 3 + 2] = (w0 * D[2] + w1 * D[4]) + w2 * D[5];
-            if (diag) acc[36 + a] = acc[36 + a] + ((w0 * D[6] + w1 * D[7]) + w2 * D[8]);
-          }
-          double W2[18];
-          edge_W(W.e_lin + (size_t)e2 * kEdgeWords, W2);
-          SIM3_UNROLL
-          for (int a = 0; a < 6; ++a)
-            SIM3_UNROLL
-            for (int b = 0; b < 6; ++b) acc[a * 6 + b] = acc[a * 6 + b] + ((Y[a * 3] * W2[b * 3] + Y[a * 3 + 1] * W2[b * 3 + 1]) + Y[a * 3 + 2] * W2[b * 3 + 2]);
-        }
-      },
-      S);
+  T.template sum_shared<kSchurSums>([&](int l, double* acc) { schur_accumulate(W, i1, i2, l, acc); }, S);
   const int N = 6 * W.F;
   const double lambda = W.ctl->lambda;
   const bool on = W.f_on[i1] && W.f_on[i2];
@@ -424,10 +580,7 @@ PO_HD void phase_schur(const Ws& W, Team& T, int blk) {
       } else {
         double h = 0.;
         if (diag) {
-          int idx = 0;  // index of (a, b), a <= b, in the 21 upper entries
-          for (int r = 0; r < a; ++r) idx += 6 - r;
-          idx += b - a;
-          h = W.Hpp[27 * i1 + idx];
+          h = W.Hpp[27 * i1 + tri6(a, b)];
           if (a == b) h = h + lambda;
         }
         v = MUT == kMutSchurAdd ? h + S[k] : h - S[k];
@@ -444,40 +597,8 @@ PO_HD void phase_schur(const Ws& W, Team& T, int blk) {
 template <int MUT, class Team>
 PO_HD void phase_solve(const Ws& W, Team& T, int) {
   const int N = 6 * W.F;
-  double* A = W.Hs;
-  double* col = T.vec();       // [N] column k of L
-  double* y = T.vec() + 6 * kMaxFree;  // [N]
-  bool ok = true;
-  T.par(N, [&](int i) { y[i] = W.bs[i]; });
-  PO_NOUNROLL
-  for (int k = 0; k < N; ++k) {
-    const double dk = A[(size_t)k * N + k];
-    ok = ok && dk > 0. && dk <= DBL_MAX;
-    T.par(N - k - 1, [&](int r) {
-      const int i = k + 1 + r;
-      const double v = A[(size_t)i * N + k] / dk;
-      A[(size_t)i * N + k] = v, col[i] = v;
-    });
-    T.par2(N - k - 1, N - k - 1, [&](int r, int c) {
-      if (c > r) return;
-      const int i = k + 1 + r, j = k + 1 + c;
-      A[(size_t)i * N + j] = A[(size_t)i * N + j] - (col[i] * col[j]) * dk;
-    });
-  }
-  PO_NOUNROLL
-  for (int k = 0; k < N; ++k) {
-    const double yk = y[k];
-    T.par(N - k - 1, [&](int r) {
-      const int i = k + 1 + r;
-      y[i] = y[i] - A[(size_t)i * N + k] * yk;
-    });
-  }
-  T.par(N, [&](int i) { y[i] = y[i] / A[(size_t)i * N + i]; });
-  PO_NOUNROLL
-  for (int k = N - 1; k >= 1; --k) {
-    const double xk = y[k];
-    T.par(k, [&](int i) { y[i] = y[i] - A[(size_t)k * N + i] * xk; });
-  }
+  double* y = T.vec() + 6 * kMaxFree;  // [N]; T.vec(): [N] column k of L
+  const bool ok = ldlt_solve(T, W.Hs, N, W.bs, T.vec(), y);
   if (ok) T.par(N, [&](int i) { W.xp[i] = y[i]; });
   // on a failed solve the step keeps its previous value and is applied all the same, as update(_solver->x()) is
   T.par(W.K, [&](int kf) {
@@ -499,48 +620,19 @@ PO_HD void phase_step(const Ws& W, Team& T, int blk) {
       [&](int l, double* acc) {
         const int j = blk * kLanes + l;
         if (j >= W.P) return;
-        double* X = W.X + 3 * (size_t)j;
-        double* Xt = W.X_try + 3 * (size_t)j;
-        double* xl = W.xl + 3 * (size_t)j;
         if (!W.p_on[j]) {
           // outside the system: it keeps its estimate (the mutation applies the step the last optimize() left)
           SIM3_UNROLL
-          for (int b = 0; b < 3; ++b) Xt[b] = MUT == kMutStepIdle ? X[b] + xl[b] : X[b];
+          for (int b = 0; b < 3; ++b) W.X_try[3 * (size_t)j + b] = MUT == kMutStepIdle ? W.X[3 * (size_t)j + b] + W.xl[3 * (size_t)j + b] : W.X[3 * (size_t)j + b];
           return;
         }
-        const double* H = W.Hll + 9 * (size_t)j;
-        if (ok) {
-          double c[3] = {H[6], H[7], H[8]};
-          if (MUT != kMutNoWx) {
-            PO_NOUNROLL
-            for (int e = W.pt_begin[j]; e < W.pt_begin[j + 1]; ++e) {
-              if (W.e_off[e]) continue;
-              const int f = free_of<MUT>(W, e);
-              if (f < 0 || !W.f_on[f]) continue;
-              double Wm[18];
-              edge_W(W.e_lin + (size_t)e * kEdgeWords, Wm);
-              const double* x = W.xp + 6 * f;
-              SIM3_UNROLL
-              for (int b = 0; b < 3; ++b) {
-                double t = Wm[b] * -x[0];
-                SIM3_UNROLL
-                for (int a = 1; a < 6; ++a) t = t + Wm[a * 3 + b] * -x[a];
-                c[b] = c[b] + t;
-              }
-            }
-          }
-          const double* D = W.Dinv + 9 * (size_t)j;
-          xl[0] = (D[0] * c[0] + D[1] * c[1]) + D[2] * c[2];
-          xl[1] = (D[1] * c[0] + D[3] * c[1]) + D[4] * c[2];
-          xl[2] = (D[2] * c[0] + D[4] * c[1]) + D[5] * c[2];
-        }
-        double t = 0.;
-        SIM3_UNROLL
-        for (int b = 0; b < 3; ++b) {
-          Xt[b] = X[b] + xl[b];
-          t = t + xl[b] * (lambda_l * xl[b] + H[6 + b]);
-        }
-        acc[0] = acc[0] + t;
+        acc[0] = acc[0] + point_step(W, j, ok, lambda_l, [&](int e, double* x) {
+          const int f = free_of<MUT>(W, e);
+          if (MUT == kMutNoWx || f < 0 || !W.f_on[f]) return false;
+          SIM3_UNROLL
+          for (int a = 0; a < 6; ++a) x[a] = W.xp[6 * f + a];
+          return true;
+        });
       },
       &s);
   if (T.lead()) W.chunk_scale[blk] = s;
@@ -601,37 +693,7 @@ PO_HD void phase_trial_ctl(const Ws& W, Team& T, int) {
       W.e_chi2[e] = E.chi2;
     });
   }
-  if (T.lead()) {
-    if (c.n_trials < kMaxTrialRecs) {
-      poseopt::TraceTrial& r = W.trace->trial[c.n_trials];
-      r.lin = c.n_lin - 1, r.ok = ok ? 1 : 0, r.accepted = accept ? 1 : 0, r.pad_ = 0;
-      r.lambda = lambda, r.cur = cur, r.tmp = tmp, r.scale = scale;
-    }
-    c.n_trials = c.n_trials + 1;
-    W.trace->n_trials = c.n_trials;
-    double ni = c.ni, lam = lambda, now = cur;
-    if (accept) {
-      const double u = 2. * rho - 1.;
-      double alpha = 1. - u * u * u;
-      alpha = 2. / 3. < alpha ? 2. / 3. : alpha;
-      const double sf = 1. / 3. < alpha ? alpha : 1. / 3.;
-      lam = lam * sf, ni = 2., now = tmp;
-    } else {
-      lam = lam * ni, ni = ni * 2.;
-    }
-    const int q = c.q + 1;
-    c.lambda = lam, c.ni = ni, c.cur = now, c.rho = rho, c.q = q;
-    if (rho < 0. && q < kMaxTrials) {
-      c.status = kStTrial;
-    } else if (q == kMaxTrials || rho == 0.) {  // Terminate
-      c.status = kStStop;
-    } else {
-      if ((c.ini - now) * 1e3 < c.ini) c.stalled = c.stalled + 1;
-      else c.stalled = 0;
-      c.status = c.stalled >= 3 ? kStStop : kStLinearise;
-      c.it = c.it + 1;
-    }
-  }
+  if (T.lead()) levenberg_decide(W, lambda, cur, ok, tmp, scale, rho, accept);
 }
 
 // chi2() > 5.991 || !isDepthPositive(): chi2 of the stored error, the depth at the current estimates; edges of points flagged bad are
@@ -773,10 +835,11 @@ inline int derive(int K, const uint8_t* fixed, int P, const int32_t* pt_begin, i
   return 0;
 }
 
-// the host's team: lane_team.hpp's walk of the reduction shape, one thread that plays lanes 0..255 in turn
+// the host's team, of this core and of navba_core.hpp: lane_team.hpp's walk of the reduction shape, one thread that plays lanes
+// 0..255 in turn
 #if !defined(__HIP_DEVICE_COMPILE__)
 struct HostTeam : HostLaneTeam<kSchurSums> {
-  double v[2 * 6 * kMaxFree];
+  double v[2 * 6 * kMaxFree];  // the solve's two vectors; navba_core.hpp asserts that its own fit
   double* vec() { return v; }
   template <class F>
   double maxr(F f) {
@@ -787,6 +850,10 @@ struct HostTeam : HostLaneTeam<kSchurSums> {
   template <class F>
   void par(int n, F f) {
     for (int i = 0; i < n; ++i) f(i);
+  }
+  template <class F>
+  void each(int n, F f) {  // navopt_core.hpp's name for par
+    par(n, f);
   }
   template <class F>
   void par2(int rows, int cols, F f) {

@@ -2,7 +2,10 @@
 // NavState.cpp, so3.cpp and g2o it runs: a window of key frames with 15 unknowns each (VertexNavStatePVR dP dV dPhi, VertexNavStateBias
 // dbg dba), chained by EdgeNavStatePVR and EdgeNavStateBias, with EdgeNavStateDepthProjected entries, under marginalised points seen
 // through EdgeNavStatePVRPointXYZ.  It joins ba_core.hpp (points eliminated, the Schur complement rebuilt per trial, the dense LDL^T,
-// the Levenberg driver as launches) and navopt_core.hpp (NavState, SO3, the inertial edges), whose helpers it calls.  Plain C++ in
+// the Levenberg driver as launches) and navopt_core.hpp (NavState, SO3, the inertial edges) BY CALLING THEM: the per-point and
+// per-key-frame sums, Dinv, the Schur block's sums, the solve, the point back-substitution and the Levenberg bookkeeping are
+// ba_core.hpp's "Schur pieces", stated there once; this file owns the mono edge through the NavState camera, the inertial edges,
+// inert_lin / inert_add / inert_err, the 15-block scatter, hdiag, bfull and the two checks.  Plain C++ in
 // double under poseopt_core.hpp's rules: IEEE + - * / sqrt fabs only, no contraction, no library function.  navba.hip runs this on the
 // device, tests/emu/navba_emu.cpp on the host; the two are held to each other bit for bit.
 //
@@ -45,11 +48,12 @@ using poseopt::kLanes;
 using ba::chunks;
 using ba::max_nan;
 using ba::schur_blocks;
+using ba::tri6;
 
 constexpr int kMaxFree = 24, kMaxFixed = 256, kMaxPoints = 32768, kMaxEdges = 262144, kMaxCams = 64, kMaxDepth = 256;
 constexpr int kMaxLinks = 2 * kMaxFree;        // one per window key frame, the ones fixed by fixedKF_id included
-constexpr int kMaxTrials = 10;
-constexpr int kMaxLin = 32, kMaxTrialRecs = 320;
+constexpr int kMaxTrials = ba::kMaxTrials;
+constexpr int kMaxLin = ba::kMaxLin, kMaxTrialRecs = ba::kMaxTrialRecs;
 constexpr int kSchurSums = ba::kSchurSums, kEdgeWords = ba::kEdgeWords;
 constexpr int kJ = 30;                           // columns of an inertial edge's Jacobian
 constexpr int kIeJ = 0, kIeWJ = 9 * kJ, kIeE = 2 * 9 * kJ, kIeWe = kIeE + 9, kIeChi = kIeWe + 9, kIeWords = kIeChi + 4;  // chi2 rho0 rho1
@@ -63,11 +67,7 @@ enum Phase { kInit = 0, kBegin, kEdgeLin, kInertLin, kPointSum, kKfSum, kLinCtl,
 constexpr int kStTrial = ba::kStTrial, kStLinearise = ba::kStLinearise, kStStop = ba::kStStop;
 
 using TraceLin = ba::TraceLin;   // n_edges counts the inertial edges too; n_free is F
-struct Trace {
-  int32_t n_lin, n_trials;
-  TraceLin lin[kMaxLin];
-  poseopt::TraceTrial trial[kMaxTrialRecs];
-};
+using Trace = ba::Trace;
 using Ctl = ba::Ctl;
 
 struct Link {    // one inertial link: kf1's preintegration, measured from kf0
@@ -153,11 +153,6 @@ PO_HD int mono_of(int a) {
   if (p < 0 || p >= 9) return -1;
   if (MUT == kMutScatter05) return p < 6 ? p : -1;
   return p < 3 ? p : p >= 6 ? p - 3 : -1;
-}
-PO_HD int tri6(int a, int b) {  // index of (a, b), a <= b, among the 21 upper entries
-  int idx = 0;
-  for (int r = 0; r < a; ++r) idx += 6 - r;
-  return idx + (b - a);
 }
 
 // ---- EdgeNavStatePVRPointXYZ g2otypes.h:207-281, g2otypes.cpp:394-449 ------------------------------------------------------------------
@@ -473,11 +468,7 @@ PO_HD void phase_init(const Ws& W, Team& T, int blk) {
       double Rcb[9];
       navopt::mat3_t(W.prm->Rbc, Rcb);
       navopt::mat3_vec(Rcb, W.prm->Pbc, W.camc);
-      Ctl& c = *W.ctl;
-      c.lambda = 0., c.ni = 2., c.cur = 0., c.ini = 0., c.rho = 0.;
-      c.round = -1, c.it = 0, c.q = 0, c.stalled = 0, c.status = 0, c.solve_ok = 0, c.n_lin = 0, c.n_trials = 0;
-      c.its[0] = c.its[1] = 0;
-      W.trace->n_lin = 0, W.trace->n_trials = 0;
+      ba::ctl_reset(W);
     }
   });
   if (blk < W.L) {  // CovPVPhi.inverse() of link blk: navopt_core.hpp's LDL^T, column by column of the identity
@@ -547,26 +538,10 @@ PO_HD void phase_point_sum(const Ws& W, Team& T, int blk) {
   const double mx = T.maxr([&](int l) {
     const int j = blk * kLanes + l;
     if (j >= W.P) return 0.;
-    double H[9] = {0., 0., 0., 0., 0., 0., 0., 0., 0.};
-    int on = 0;
-    PO_NOUNROLL
-    for (int e = W.pt_begin[j]; e < W.pt_begin[j + 1]; ++e) {
-      if (W.e_off[e]) continue;
-      on = 1;
-      const double* L = W.e_lin + (size_t)e * kEdgeWords;
-      int k = 0;
-      SIM3_UNROLL
-      for (int a = 0; a < 3; ++a)
-        SIM3_UNROLL
-        for (int b = a; b < 3; ++b, ++k) H[k] = H[k] + ((L[12 + a] * L[18]) * L[12 + b] + (L[15 + a] * L[18]) * L[15 + b]);
-      SIM3_UNROLL
-      for (int a = 0; a < 3; ++a) H[6 + a] = H[6 + a] + (L[12 + a] * L[19] + L[15 + a] * L[20]);
-    }
-    SIM3_UNROLL
-    for (int k = 0; k < 9; ++k) W.Hll[9 * (size_t)j + k] = H[k];
-    W.p_on[j] = (uint8_t)on;
+    double H[9];
+    const bool on = ba::point_sum(W, j, H);
     if (MUT == kMutTauPoses || !on) return 0.;
-    return max_nan(max_nan(fabs(H[0]), fabs(H[3])), fabs(H[5]));
+    return ba::point_maxdiag(H);
   });
   if (T.lead()) W.chunk_max[blk] = mx;
 }
@@ -575,23 +550,7 @@ template <int MUT, class Team>
 PO_HD void phase_kf_sum(const Ws& W, Team& T, int f) {
   const int b0 = W.kl_begin[f], n = W.kl_begin[f + 1] - b0;
   double S[27];
-  T.template sum<27>(
-      [&](int l, double* acc) {
-        PO_NOUNROLL
-        for (int i = l; i < n; i += kLanes) {
-          const int e = W.kl_edge[b0 + i];
-          if (W.e_off[e]) continue;
-          const double* L = W.e_lin + (size_t)e * kEdgeWords;
-          int k = 0;
-          SIM3_UNROLL
-          for (int a = 0; a < 6; ++a)
-            SIM3_UNROLL
-            for (int b = a; b < 6; ++b, ++k) acc[k] = acc[k] + ((L[a] * L[18]) * L[b] + (L[6 + a] * L[18]) * L[6 + b]);
-          SIM3_UNROLL
-          for (int a = 0; a < 6; ++a) acc[21 + a] = acc[21 + a] + (L[a] * L[19] + L[6 + a] * L[20]);
-        }
-      },
-      S);
+  T.template sum<27>([&](int l, double* acc) { ba::kf_accumulate(W, b0, n, l, acc); }, S);
   if (T.lead()) {
     SIM3_UNROLL
     for (int k = 0; k < 27; ++k) W.Hpp[27 * f + k] = S[k];
@@ -630,25 +589,13 @@ PO_HD void phase_lin_ctl(const Ws& W, Team& T, int) {
     return c;
   });
   if (T.lead()) {
-    Ctl& c = *W.ctl;
     const int G = n_inert(W);
     double chi = 0.;
     PO_NOUNROLL
     for (int i = 0; i < ce; ++i) chi = chi + W.chunk_chi2[i];
     PO_NOUNROLL
     for (int g = 0; g < G; ++g) chi = chi + W.ie_lin[(size_t)g * kIeWords + kIeChi + 1];
-    c.cur = chi, c.ini = chi;
-    if (c.it == 0) c.lambda = 1e-5 * mx, c.ni = 2., c.stalled = 0;
-    c.q = 0, c.rho = 0.;
-    if (c.n_lin < kMaxLin) {
-      TraceLin& r = W.trace->lin[c.n_lin];
-      r.round = c.round, r.iteration = c.it, r.n_edges = n_mono + G, r.n_free = W.F, r.n_points = n_points, r.pad_ = 0;
-      r.chi2 = chi, r.maxdiag = mx;
-    }
-    c.n_lin = c.n_lin + 1;
-    W.trace->n_lin = c.n_lin;
-    c.its[c.round] = c.its[c.round] + 1;
-    c.status = kStTrial;
+    ba::levenberg_linearised(W, chi, mx, n_mono + G, W.F, n_points);
   }
 }
 
@@ -657,19 +604,7 @@ PO_HD void phase_dinv(const Ws& W, Team& T, int blk) {
   const double lambda = W.ctl->lambda;
   T.par(kLanes, [&](int l) {
     const int j = blk * kLanes + l;
-    if (j >= W.P || !W.p_on[j]) return;
-    // Dinv = (Hll + lambda I)^-1 as the adjugate over the determinant, as ba::point_dinv
-    const double* H = W.Hll + 9 * (size_t)j;
-    const double m00 = H[0] + lambda, m01 = H[1], m02 = H[2], m11 = H[3] + lambda, m12 = H[4], m22 = H[5] + lambda;
-    const double c00 = m11 * m22 - m12 * m12, c01 = m12 * m02 - m01 * m22, c02 = m01 * m12 - m11 * m02;
-    const double c11 = m00 * m22 - m02 * m02, c12 = m01 * m02 - m00 * m12, c22 = m00 * m11 - m01 * m01;
-    const double det = (m00 * c00 + m01 * c01) + m02 * c02;
-    const double inv = 1. / det;
-    double* D = W.Dinv + 9 * (size_t)j;
-    D[0] = c00 * inv, D[1] = c01 * inv, D[2] = c02 * inv, D[3] = c11 * inv, D[4] = c12 * inv, D[5] = c22 * inv;
-    D[6] = (D[0] * H[6] + D[1] * H[7]) + D[2] * H[8];
-    D[7] = (D[1] * H[6] + D[3] * H[7]) + D[4] * H[8];
-    D[8] = (D[2] * H[6] + D[4] * H[7]) + D[5] * H[8];
+    if (j < W.P && W.p_on[j]) ba::point_dinv(W, j, lambda);
   });
 }
 
@@ -678,41 +613,11 @@ PO_HD void phase_dinv(const Ws& W, Team& T, int blk) {
 // on the diagonal, zero elsewhere.  inert_add adds the inertial edges.
 template <int MUT, class Team>
 PO_HD void phase_schur(const Ws& W, Team& T, int blk) {
-  int i1 = 0, rest = blk;
-  while (rest >= W.F - i1) rest -= W.F - i1, ++i1;
-  const int i2 = i1 + rest;
-  const int b0 = W.kl_begin[i1], n = W.kl_begin[i1 + 1] - b0;
+  int i1, i2;
+  ba::block_of(blk, W.F, &i1, &i2);
   const bool diag = i1 == i2;
   double* S = T.shared();
-  T.template sum_shared<kSchurSums>(
-      [&](int l, double* acc) {
-        PO_NOUNROLL
-        for (int i = l; i < n; i += kLanes) {
-          const int e1 = W.kl_edge[b0 + i];
-          if (W.e_off[e1]) continue;
-          const int j = W.e_pt[e1];
-          const int e2 = diag ? e1 : W.fp_edge[(size_t)i2 * W.P + j];
-          if (e2 < 0 || W.e_off[e2]) continue;
-          const double* D = W.Dinv + 9 * (size_t)j;
-          double W1[18], Y[18];
-          ba::edge_W(W.e_lin + (size_t)e1 * kEdgeWords, W1);
-          SIM3_UNROLL
-          for (int a = 0; a < 6; ++a) {
-            const double w0 = W1[a * 3], w1 = W1[a * 3 + 1], w2 = W1[a * 3 + 2];
-            Y[a * 3] = (w0 * D[0] + w1 * D[1]) + w2 * D[2];
-            Y[a * 3 + 1] = (w0 * D[1] + w1 * D[3]) + w2 * D[4];
-            Y[a * 3 + 2] = (w0 * D[2] + w1 * D[4]) + w2 * D[5];
-            if (diag) acc[36 + a] = acc[36 + a] + ((w0 * D[6] + w1 * D[7]) + w2 * D[8]);
-          }
-          double W2[18];
-          ba::edge_W(W.e_lin + (size_t)e2 * kEdgeWords, W2);
-          SIM3_UNROLL
-          for (int a = 0; a < 6; ++a)
-            SIM3_UNROLL
-            for (int b = 0; b < 6; ++b) acc[a * 6 + b] = acc[a * 6 + b] + ((Y[a * 3] * W2[b * 3] + Y[a * 3 + 1] * W2[b * 3 + 1]) + Y[a * 3 + 2] * W2[b * 3 + 2]);
-        }
-      },
-      S);
+  T.template sum_shared<kSchurSums>([&](int l, double* acc) { ba::schur_accumulate(W, i1, i2, l, acc); }, S);
   const int N = 15 * W.F;
   const double lambda = W.ctl->lambda;
   T.par(225 + 15, [&](int k) {
@@ -742,6 +647,8 @@ PO_HD void phase_schur(const Ws& W, Team& T, int blk) {
 // the inertial edges' J^T (rho1 Omega) J and J^T (rho1 Omega) e into block (i1, i2): one lane an entry
 template <int MUT, class Team>
 PO_HD void phase_inert_add(const Ws& W, Team& T, int blk) {
+  // ba::block_of, written out: behind the call the compiler no longer sees that the columns below are not negative, and the
+  // walks of ie_sum cost this kernel 7 to 10 % (profiles/LOG.md)
   int i1 = 0, rest = blk;
   while (rest >= W.F - i1) rest -= W.F - i1, ++i1;
   const int i2 = i1 + rest;
@@ -771,40 +678,8 @@ PO_HD void phase_inert_add(const Ws& W, Team& T, int blk) {
 template <int MUT, class Team>
 PO_HD void phase_solve(const Ws& W, Team& T, int) {
   const int N = 15 * W.F;
-  double* A = W.Hs;
-  double* col = T.vec();
   double* y = T.vec() + 15 * kMaxFree;
-  bool ok = true;
-  T.par(N, [&](int i) { y[i] = W.bs[i]; });
-  PO_NOUNROLL
-  for (int k = 0; k < N; ++k) {
-    const double dk = A[(size_t)k * N + k];
-    ok = ok && dk > 0. && dk <= DBL_MAX;
-    T.par(N - k - 1, [&](int r) {
-      const int i = k + 1 + r;
-      const double v = A[(size_t)i * N + k] / dk;
-      A[(size_t)i * N + k] = v, col[i] = v;
-    });
-    T.par2(N - k - 1, N - k - 1, [&](int r, int c) {
-      if (c > r) return;
-      const int i = k + 1 + r, j = k + 1 + c;
-      A[(size_t)i * N + j] = A[(size_t)i * N + j] - (col[i] * col[j]) * dk;
-    });
-  }
-  PO_NOUNROLL
-  for (int k = 0; k < N; ++k) {
-    const double yk = y[k];
-    T.par(N - k - 1, [&](int r) {
-      const int i = k + 1 + r;
-      y[i] = y[i] - A[(size_t)i * N + k] * yk;
-    });
-  }
-  T.par(N, [&](int i) { y[i] = y[i] / A[(size_t)i * N + i]; });
-  PO_NOUNROLL
-  for (int k = N - 1; k >= 1; --k) {
-    const double xk = y[k];
-    T.par(k, [&](int i) { y[i] = y[i] - A[(size_t)k * N + i] * xk; });
-  }
+  const bool ok = ba::ldlt_solve(T, W.Hs, N, W.bs, T.vec(), y);
   if (ok) T.par(N, [&](int i) { W.xp[i] = y[i]; });
   T.par(W.K, [&](int kf) {
     const int f = W.kf_free[kf];
@@ -824,45 +699,18 @@ PO_HD void phase_step(const Ws& W, Team& T, int blk) {
       [&](int l, double* acc) {
         const int j = blk * kLanes + l;
         if (j >= W.P) return;
-        double* X = W.X + 3 * (size_t)j;
-        double* Xt = W.X_try + 3 * (size_t)j;
-        double* xl = W.xl + 3 * (size_t)j;
         if (!W.p_on[j]) {
           SIM3_UNROLL
-          for (int b = 0; b < 3; ++b) Xt[b] = X[b];
+          for (int b = 0; b < 3; ++b) W.X_try[3 * (size_t)j + b] = W.X[3 * (size_t)j + b];
           return;
         }
-        const double* H = W.Hll + 9 * (size_t)j;
-        if (ok) {
-          double c[3] = {H[6], H[7], H[8]};
-          PO_NOUNROLL
-          for (int e = W.pt_begin[j]; e < W.pt_begin[j + 1]; ++e) {
-            if (W.e_off[e]) continue;
-            const int f = W.kf_free[W.e_kf[e]];
-            if (f < 0) continue;
-            double Wm[18];
-            ba::edge_W(W.e_lin + (size_t)e * kEdgeWords, Wm);
-            const double* x = W.xp + col_pvr<MUT>(f);
-            SIM3_UNROLL
-            for (int b = 0; b < 3; ++b) {
-              double t = Wm[b] * -x[pvr_of6<MUT>(0)];
-              SIM3_UNROLL
-              for (int a = 1; a < 6; ++a) t = t + Wm[a * 3 + b] * -x[pvr_of6<MUT>(a)];
-              c[b] = c[b] + t;
-            }
-          }
-          const double* D = W.Dinv + 9 * (size_t)j;
-          xl[0] = (D[0] * c[0] + D[1] * c[1]) + D[2] * c[2];
-          xl[1] = (D[1] * c[0] + D[3] * c[1]) + D[4] * c[2];
-          xl[2] = (D[2] * c[0] + D[4] * c[1]) + D[5] * c[2];
-        }
-        double t = 0.;
-        SIM3_UNROLL
-        for (int b = 0; b < 3; ++b) {
-          Xt[b] = X[b] + xl[b];
-          t = t + xl[b] * (lambda * xl[b] + H[6 + b]);
-        }
-        acc[0] = acc[0] + t;
+        acc[0] = acc[0] + ba::point_step(W, j, ok, lambda, [&](int e, double* x) {
+          const int f = W.kf_free[W.e_kf[e]];
+          if (f < 0) return false;
+          SIM3_UNROLL
+          for (int a = 0; a < 6; ++a) x[a] = W.xp[col_pvr<MUT>(f) + pvr_of6<MUT>(a)];
+          return true;
+        });
       },
       &s);
   if (T.lead()) W.chunk_scale[blk] = s;
@@ -925,37 +773,7 @@ PO_HD void phase_trial_ctl(const Ws& W, Team& T, int) {
     T.par(12 * W.K, [&](int i) { W.cam[i] = W.cam_try[i]; });
     T.par(3 * W.P, [&](int i) { W.X[i] = W.X_try[i]; });
   }
-  if (T.lead()) {
-    if (c.n_trials < kMaxTrialRecs) {
-      poseopt::TraceTrial& r = W.trace->trial[c.n_trials];
-      r.lin = c.n_lin - 1, r.ok = ok ? 1 : 0, r.accepted = accept ? 1 : 0, r.pad_ = 0;
-      r.lambda = lambda, r.cur = cur, r.tmp = tmp, r.scale = scale;
-    }
-    c.n_trials = c.n_trials + 1;
-    W.trace->n_trials = c.n_trials;
-    double ni = c.ni, lam = lambda, now = cur;
-    if (accept) {
-      const double u = 2. * rho - 1.;
-      double alpha = 1. - u * u * u;
-      alpha = 2. / 3. < alpha ? 2. / 3. : alpha;
-      const double sf = 1. / 3. < alpha ? alpha : 1. / 3.;
-      lam = lam * sf, ni = 2., now = tmp;
-    } else {
-      lam = lam * ni, ni = ni * 2.;
-    }
-    const int q = c.q + 1;
-    c.lambda = lam, c.ni = ni, c.cur = now, c.rho = rho, c.q = q;
-    if (rho < 0. && q < kMaxTrials) {
-      c.status = kStTrial;
-    } else if (q == kMaxTrials || rho == 0.) {  // Terminate
-      c.status = kStStop;
-    } else {
-      if ((c.ini - now) * 1e3 < c.ini) c.stalled = c.stalled + 1;
-      else c.stalled = 0;
-      c.status = c.stalled >= 3 ? kStStop : kStLinearise;
-      c.it = c.it + 1;
-    }
-  }
+  if (T.lead()) ba::levenberg_decide(W, lambda, cur, ok, tmp, scale, rho, accept);
 }
 
 // chi2() > 5.991 || !isDepthPositive() on the stored chi2 and the depth at the current estimates; edges of flagged points are not
@@ -1087,12 +905,7 @@ inline int check_inertial(int K, const uint8_t* fixed, const uint8_t* has_bias, 
 }
 
 #if !defined(__HIP_DEVICE_COMPILE__)
-struct HostTeam : ba::HostTeam {
-  template <class F>
-  void each(int count, F f) {
-    for (int i = 0; i < count; ++i) f(i);
-  }
-};
+using HostTeam = ba::HostTeam;
 static_assert(2 * 15 * kMaxFree <= 2 * 6 * ba::kMaxFree, "the solve's two vectors fit ba::HostTeam's");
 #endif
 
