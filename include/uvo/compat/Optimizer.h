@@ -17,7 +17,27 @@
 //
 // and an overload over the list of candidates that issues ONE device call; the caller takes the first candidate in order with
 // nInliers >= 10.  With it the path from loop candidate to accepted loop links nothing of the reference's Optimizer.
-// OptimizeEssentialGraph, GlobalBundleAdjustmentNavState and the initialisation optimisers stay with the reference's Optimizer.
+// GlobalBundleAdjustmentNavState and the initialisation optimisers stay with the reference's Optimizer (the first has no caller).
+//
+// Optimizer::OptimizeEssentialGraph(pMap, pLoopKF, pCurKF, Scurw, NonCorrectedSim3, CorrectedSim3, LoopConnections)
+// (src/Optimizer.cc:2409-2658, called at src/LoopClosing.cc:678) over the C ABI's essential graph (uvo_essential_graph_* in uvo/uvo.h):
+//
+//     - Optimizer::OptimizeEssentialGraph(mpMap, mpMatchedKF, mpCurrentKF, mg2oScw, NonCorrectedSim3, CorrectedSim3, LoopConnections);
+//     + USLAM::Optimizer::OptimizeEssentialGraph(graph, mpMap, mpMatchedKF, mpCurrentKF, mScw, NonCorrectedSim3, CorrectedSim3, LoopConnections);
+//
+// graph: a USLAM::EssentialGraphOptimizer; KeyFrameAndPose: any std::map<KF*, USLAM::Sim3>.  It needs of the map GetAllKeyFrames() and
+// GetAllMapPoints(); of the key-frame type mnId, isBad(), GetRotation(), GetTranslation(), GetParent(), GetLoopEdges() (a std::set<KF*>),
+// GetCovisiblesByWeight(w), GetWeight(pKF), hasChild(pKF); of the map-point type isBad(), mnCorrectedByKF, mnCorrectedReference,
+// GetReferenceKeyFrame(), GetWorldPos(), UpdateNormalAndDepth().  The reference's walk is kept (:2437-2598): the vertices are the key
+// frames that are not bad, in ascending mnId (the order the envelope solver is given); the edges in the order of insertion -- those of
+// LoopConnections in the map's and the sets' iteration order under the weight rule of :2489, then per key frame of GetAllKeyFrames()
+// the parent edge, the loop edges to smaller ids and the covisibility edges of GetCovisiblesByWeight(100) under the conditions of
+// :2574-2579 with the inserted-pairs set -- and its effects (:2605-2657): ba_set_pose with [R | t / s], ba_set_world_pos +
+// UpdateNormalAndDepth() per map point that is not bad, nIDr chosen as :2635-2643 choose it.  Departures: a bad key frame is no vertex,
+// and where the reference dereferences the null optimizer.vertex(id) for it the adaptor skips that edge or key frame; the normal-edge
+// loop skips bad key frames; a point whose reference key frame is no vertex keeps its position (the reference maps it through two
+// default-constructed similarities, the identity) and is still set and updated; on a failed library call, or when pLoopKF is no
+// vertex, -1 is returned and nothing of the caller's is touched.  Scurw is taken and not read, as in the reference.
 //
 // The two IMU overloads of Optimizer::PoseOptimization (src/Optimizer.cc:779-1103 over a key frame, :319-777 over the last frame) over
 // the C ABI's nav optimizer (uvo_nav_* in uvo/uvo.h), for Tracking::TrackWithIMU (src/Tracking.cc:1099, :1105), TrackLocalMapWithIMU
@@ -100,8 +120,12 @@
 // Header only, C++11, no OpenCV.
 #ifndef UVO_COMPAT_OPTIMIZER_H_
 #define UVO_COMPAT_OPTIMIZER_H_
+#include <algorithm>
 #include <cmath>
+#include <map>
+#include <set>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "uvo/uvo.h"
@@ -1021,6 +1045,171 @@ int LocalBundleAdjustmentNavState(KF* pCurKF, const List& lLocalKeyFrames, bool*
     }
   }
   if (pLM) pLM->SetMapUpdateFlagInTracking(true);
+  return 0;
+}
+
+}  // namespace Optimizer
+
+// the owner of the device graph: one on the loop-closing thread's matcher handle; the sizes in the order of uvo_essential_graph_create
+class EssentialGraphOptimizer {
+ public:
+  EssentialGraphOptimizer(uvo_matcher* m, int max_keyframes, int max_edges, int max_envelope_blocks, int max_points) : g_(0) {
+    uvo_essential_graph_create(m, max_keyframes, max_edges, max_envelope_blocks, max_points, &g_);
+  }
+  ~EssentialGraphOptimizer() { uvo_essential_graph_destroy(g_); }
+  bool ok() const { return g_ != 0; }
+  uvo_essential_graph* handle() { return g_; }
+  // gathering buffers, kept between calls so that a call allocates nothing once they have grown
+  std::vector<uvo_sim3d> Scw, Scw_normal, Scw_out;
+  std::vector<int32_t> edge_i, edge_j, point_ref;
+  std::vector<uint8_t> edge_connection;
+  std::vector<float> points, Tcw_out, points_out;
+  uvo_essential_result result;  // of the last call: iterations, trials, envelope blocks
+
+ private:
+  EssentialGraphOptimizer(const EssentialGraphOptimizer&);
+  EssentialGraphOptimizer& operator=(const EssentialGraphOptimizer&);
+  uvo_essential_graph* g_;
+};
+
+namespace detail {
+inline uvo_sim3d sim3d_of(const Sim3& S) {
+  uvo_sim3d o;
+  for (int e = 0; e < 4; ++e) o.q[e] = S.quaternion()[e];
+  for (int e = 0; e < 3; ++e) o.t[e] = S.translation()[e];
+  o.s = S.scale();
+  return o;
+}
+// g2o::Sim3 Siw(Rcw, tcw, 1.0) of the key frame's float pose
+template <class KF>
+uvo_sim3d sim3d_of_pose(KF* pKF) {
+  const auto R = pKF->GetRotation();
+  const auto t = pKF->GetTranslation();
+  float Rf[9], tf[3];
+  for (int e = 0; e < 9; ++e) Rf[e] = mat_elem(R, e, 0);
+  for (int e = 0; e < 3; ++e) tf[e] = mat_elem(t, e, 0);
+  return sim3d_of(Sim3(Rf, tf, 1.f));
+}
+template <class KF>
+struct ById {
+  bool operator()(const KF* a, const KF* b) const { return a->mnId < b->mnId; }
+};
+}  // namespace detail
+
+namespace Optimizer {
+
+template <class Map, class KF, class KeyFrameAndPose, class Connections>
+int OptimizeEssentialGraph(EssentialGraphOptimizer& g, Map* pMap, KF* pLoopKF, KF* pCurKF, const Sim3& /*Scurw*/, const KeyFrameAndPose& NonCorrectedSim3,
+                           const KeyFrameAndPose& CorrectedSim3, const Connections& LoopConnections) {
+  const auto vpKFs = pMap->GetAllKeyFrames();
+  const auto vpMPs = pMap->GetAllMapPoints();
+  const int minFeat = 100;
+  // SET KEYFRAME VERTICES (:2437-2470), in ascending mnId
+  std::vector<KF*> vertices;
+  for (size_t i = 0; i < vpKFs.size(); i++)
+    if (!vpKFs[i]->isBad()) vertices.push_back(vpKFs[i]);
+  std::sort(vertices.begin(), vertices.end(), detail::ById<KF>());
+  std::map<KF*, int32_t> index;
+  g.Scw.clear(), g.Scw_normal.clear(), g.edge_i.clear(), g.edge_j.clear(), g.edge_connection.clear(), g.points.clear(), g.point_ref.clear();
+  for (size_t k = 0; k < vertices.size(); ++k) {
+    KF* pKF = vertices[k];
+    index[pKF] = (int32_t)k;
+    const auto c = CorrectedSim3.find(pKF);
+    g.Scw.push_back(c != CorrectedSim3.end() ? detail::sim3d_of(c->second) : detail::sim3d_of_pose(pKF));
+    const auto n = NonCorrectedSim3.find(pKF);
+    g.Scw_normal.push_back(n != NonCorrectedSim3.end() ? detail::sim3d_of(n->second) : g.Scw.back());
+  }
+  if (!index.count(pLoopKF)) return -1;
+  struct Add {
+    EssentialGraphOptimizer& g;
+    const std::map<KF*, int32_t>& index;
+    bool operator()(KF* i, KF* j, bool connection) const {  // vertex 0 = i, vertex 1 = j; false: one of them is no vertex
+      const typename std::map<KF*, int32_t>::const_iterator a = index.find(i), b = index.find(j);
+      if (a == index.end() || b == index.end()) return false;
+      g.edge_i.push_back(a->second), g.edge_j.push_back(b->second), g.edge_connection.push_back(connection ? 1 : 0);
+      return true;
+    }
+  } add = {g, index};
+  std::set<std::pair<long unsigned int, long unsigned int> > sInsertedEdges;
+  // SET LOOP EDGES (:2477-2506)
+  for (auto mit = LoopConnections.begin(), mend = LoopConnections.end(); mit != mend; mit++) {
+    KF* pKF = mit->first;
+    const long unsigned int nIDi = pKF->mnId;
+    const auto& spConnections = mit->second;
+    for (auto sit = spConnections.begin(), send = spConnections.end(); sit != send; sit++) {
+      const long unsigned int nIDj = (*sit)->mnId;
+      if ((nIDi != pCurKF->mnId || nIDj != pLoopKF->mnId) && pKF->GetWeight(*sit) < minFeat) continue;
+      if (!add(pKF, *sit, true)) continue;
+      sInsertedEdges.insert(std::make_pair(std::min(nIDi, nIDj), std::max(nIDi, nIDj)));
+    }
+  }
+  // SET NORMAL EDGES (:2508-2598)
+  for (size_t i = 0, iend = vpKFs.size(); i < iend; i++) {
+    KF* pKF = vpKFs[i];
+    if (pKF->isBad()) continue;
+    KF* pParentKF = pKF->GetParent();
+    if (pParentKF) add(pKF, pParentKF, false);  // Spanning tree edge
+    const std::set<KF*> sLoopEdges = pKF->GetLoopEdges();
+    for (auto sit = sLoopEdges.begin(), send = sLoopEdges.end(); sit != send; sit++) {
+      KF* pLKF = *sit;
+      if (pLKF->mnId < pKF->mnId) add(pKF, pLKF, false);
+    }
+    const std::vector<KF*> vpConnectedKFs = pKF->GetCovisiblesByWeight(minFeat);
+    for (auto vit = vpConnectedKFs.begin(); vit != vpConnectedKFs.end(); vit++) {
+      KF* pKFn = *vit;
+      if (pKFn && pKFn != pParentKF && !pKF->hasChild(pKFn) && !sLoopEdges.count(pKFn)) {
+        if (!pKFn->isBad() && pKFn->mnId < pKF->mnId) {
+          if (sInsertedEdges.count(std::make_pair(std::min(pKF->mnId, pKFn->mnId), std::max(pKF->mnId, pKFn->mnId)))) continue;
+          add(pKF, pKFn, false);
+        }
+      }
+    }
+  }
+  // the points that are corrected (:2627-2647); a point whose reference key frame is no vertex stays where it is
+  typedef typename std::remove_pointer<typename std::remove_reference<decltype(vpMPs[0])>::type>::type MPc;
+  typedef typename std::remove_const<MPc>::type MP;
+  std::vector<MP*> points, kept;
+  for (size_t i = 0, iend = vpMPs.size(); i < iend; i++) {
+    MP* pMP = vpMPs[i];
+    if (pMP->isBad()) continue;
+    KF* pRefKF = 0;
+    long unsigned int nIDr;
+    if (pMP->mnCorrectedByKF == pCurKF->mnId) nIDr = pMP->mnCorrectedReference;
+    else pRefKF = pMP->GetReferenceKeyFrame(), nIDr = pRefKF->mnId;
+    int32_t ref = -1;
+    for (size_t k = 0; k < vertices.size() && ref < 0; ++k)
+      if (vertices[k]->mnId == nIDr) ref = (int32_t)k;
+    if (ref < 0) {
+      kept.push_back(pMP);
+      continue;
+    }
+    float X[3];
+    detail::world_pos(pMP->GetWorldPos(), X);
+    g.points.insert(g.points.end(), X, X + 3);
+    g.point_ref.push_back(ref);
+    points.push_back(pMP);
+  }
+  // OPTIMIZE (:2602-2603)
+  const int32_t K = (int32_t)vertices.size(), E = (int32_t)g.edge_i.size(), P = (int32_t)points.size();
+  g.Scw_out.resize((size_t)K), g.Tcw_out.resize(16 * (size_t)K), g.points_out.resize(3 * (size_t)P + 1);
+  uvo_essential_problem q;
+  q.n_keyframes = K, q.n_edges = E, q.n_points = P, q.fixed = index[pLoopKF];
+  q.Scw = g.Scw.data(), q.Scw_normal = g.Scw_normal.data(), q.edge_i = g.edge_i.data(), q.edge_j = g.edge_j.data(), q.edge_connection = g.edge_connection.data();
+  q.points = g.points.data(), q.point_ref = g.point_ref.data(), q.n_iterations = 20;
+  g.result.Scw = g.Scw_out.data(), g.result.kf_Tcw = g.Tcw_out.data(), g.result.points = g.points_out.data();
+  if (!g.ok() || uvo_essential_graph_optimize(g.handle(), &q, &g.result) != UVO_OK) return -1;
+  // SE3 Pose Recovering and the points (:2605-2657)
+  for (size_t k = 0; k < vertices.size(); ++k) ba_set_pose(vertices[k], &g.Tcw_out[16 * k]);
+  for (size_t j = 0; j < points.size(); ++j) {
+    ba_set_world_pos(points[j], &g.points_out[3 * j]);
+    points[j]->UpdateNormalAndDepth();
+  }
+  for (size_t j = 0; j < kept.size(); ++j) {
+    float X[3];
+    detail::world_pos(kept[j]->GetWorldPos(), X);
+    ba_set_world_pos(kept[j], X);
+    kept[j]->UpdateNormalAndDepth();
+  }
   return 0;
 }
 

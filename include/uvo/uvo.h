@@ -1550,6 +1550,63 @@ int uvo_nav_bundle_adjust(uvo_nav_bundle_adjuster* a, const uvo_nav_ba_problem* 
 /* test tap: the trace of the adjuster's last call (no record when that call optimised nothing). */
 int uvo_nav_bundle_adjuster_trace(uvo_nav_bundle_adjuster* a, uvo_nav_ba_trace* out);
 
+/* ------------------------------------------------------------------------------------------------
+ * Essential-graph optimisation -- replaces Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:2409-2658, called at
+ * src/LoopClosing.cc:678) for a caller that has gathered the graph, with the parts of g2o it runs: one VertexSim3Expmap per key frame
+ * (scale free: _fix_scale stays false; the loop key frame fixed), one EdgeSim3 per edge with the measurement S_j * S_i^-1, information
+ * I_7, no robust kernel and BaseBinaryEdge's numeric Jacobian (delta 1e-9, central), the Levenberg driver with
+ * setUserLambdaInit(1e-16), then the SE3 poses [R | t / s] and every map point as correctedSwr.map(Srw.map(X)).
+ * Key frames stand in ascending mnId (the adaptor's order); the system is solved by an unpivoted block-envelope LDL^T in that order:
+ * row i of 7 x 7 blocks holds the blocks first(i) .. i, first(i) the smallest free index an edge joins to i.  The handle is sized in
+ * such blocks, and a graph whose envelope needs more is refused with UVO_E_CAPACITY (uvo_last_error() names both counts).
+ * The phases of a call are separate launches in the handle's stream; the Levenberg decision is made on the device and the host reads
+ * one status word per trial (n_syncs counts those reads and the download's synchronise).  Nothing is allocated per call.
+ * Departures from the reference; parity with a built g2o is not pinned, g2o not being available to the project:
+ *   - the envelope LDL^T in key-frame order fails unless every pivot is finite and > 0, where the reference runs SimplicialLDLT under
+ *     an AMD ordering; a failed solve makes the trial's chi2 DBL_MAX and the step keeps its last value;
+ *   - every sum has one fixed shape that depends on indices alone (csrc/essential_core.hpp), not g2o's order over its containers;
+ *   - sin, cos, acos, exp and log are the library's own (2^-50 or better); a scale outside 2^-60 .. 2^60 gives a NaN trial.
+ * Agreement with the model (tests/essential_model.py) is to a tolerance, agreement between the device and the host build of the same
+ * source (tests/emu/essential_emu.cpp) is bit for bit.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct uvo_essential_graph uvo_essential_graph;
+typedef struct uvo_sim3d {
+  double q[4]; /* x y z w, not normalised */
+  double t[3];
+  double s;
+} uvo_sim3d;
+typedef struct uvo_essential_problem {
+  int32_t n_keyframes, n_edges, n_points, fixed; /* key frames in ascending mnId; fixed: index of pLoopKF */
+  const uvo_sim3d* Scw;           /* [K] vScw: CorrectedSim3 where present, else (Rcw, tcw, 1) widened from the floats */
+  const uvo_sim3d* Scw_normal;    /* [K] NonCorrectedSim3 where present, else Scw: what the "normal" edges measure from */
+  const int32_t *edge_i, *edge_j; /* [E] in the reference's order of insertion; vertex 0 = i, vertex 1 = j */
+  const uint8_t* edge_connection; /* [E] 1: an edge of LoopConnections (measured from Scw), 0: normal (from Scw_normal) */
+  const float* points;            /* [P][3] */
+  const int32_t* point_ref;       /* [P] index of the key frame nIDr */
+  int32_t n_iterations;           /* 1..32; the reference passes 20 */
+} uvo_essential_problem;
+typedef struct uvo_essential_result {
+  uvo_sim3d* Scw; /* [K] the estimates; may be NULL */
+  float* kf_Tcw;  /* [K][16] [R | t / s] as Converter::toCvSE3 narrows it; may be NULL */
+  float* points;  /* [P][3]; may be NULL */
+  int32_t iterations, n_trials, n_syncs, envelope_blocks;
+} uvo_essential_result;
+/* test tap: uvo_ba_trace's records; per linearisation chi2 (and the largest diagonal entry, which the user's lambda leaves unused),
+ * per trial lambda, cur, tmp, scale, ok, accepted */
+typedef uvo_ba_trace uvo_essential_trace;
+
+/* max_keyframes 1..8192, max_edges 1..262144, max_envelope_blocks 1..4194304, max_points 0..1048576 (UVO_E_BADARG otherwise).  The
+ * handle lives on a uvo_matcher handle (the loop-closing thread's) and must be destroyed before it. */
+int uvo_essential_graph_create(uvo_matcher* m, int max_keyframes, int max_edges, int max_envelope_blocks, int max_points, uvo_essential_graph** out);
+void uvo_essential_graph_destroy(uvo_essential_graph* g);
+/* UVO_E_BADARG, with a message and nothing touched: null pointers, counts out of range, `fixed`, an edge's key frame or a point's
+ * reference outside [0, K), an edge with i == j.  (The problem carries no mnId: that the key frames ascend is the caller's to keep.)
+ * UVO_E_CAPACITY: more key frames, edges, points or envelope blocks than the handle was sized for.  With zero edges or a single
+ * key frame the answer is the input's: poses recovered, points mapped, no iteration. */
+int uvo_essential_graph_optimize(uvo_essential_graph* g, const uvo_essential_problem* problem, uvo_essential_result* result);
+/* test tap: the trace of the handle's last call. */
+int uvo_essential_graph_trace(uvo_essential_graph* g, uvo_essential_trace* out);
+
 /*
  * Initializer -- replaces USLAM::Initializer (include/Initializer.h, src/Initializer.cc) as Tracking::Initialize (src/Tracking.cc:1340)
  * and the recovery path (:1582) use it: the constructor on the reference frame, then Initialize(current frame, matches) until it

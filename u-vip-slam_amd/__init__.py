@@ -52,6 +52,7 @@ ABI_SYMBOLS = [
     "uvo_sim3_optimizer_create", "uvo_sim3_optimizer_destroy", "uvo_sim3_optimize", "uvo_sim3_optimizer_trace",
     "uvo_bundle_adjuster_create", "uvo_bundle_adjuster_destroy", "uvo_bundle_adjust", "uvo_bundle_adjuster_trace",
     "uvo_nav_bundle_adjuster_create", "uvo_nav_bundle_adjuster_destroy", "uvo_nav_bundle_adjust", "uvo_nav_bundle_adjuster_trace",
+    "uvo_essential_graph_create", "uvo_essential_graph_destroy", "uvo_essential_graph_optimize", "uvo_essential_graph_trace",
     "uvo_initializer_create", "uvo_initializer_destroy", "uvo_initializer_set_reference", "uvo_initializer_initialize", "uvo_initializer_hypotheses",
     "uvo_kfdb_create", "uvo_kfdb_destroy", "uvo_kfdb_add", "uvo_kfdb_erase", "uvo_kfdb_clear", "uvo_kfdb_set_covisibles", "uvo_kfdb_detect_reloc",
     "uvo_kfdb_detect_loop", "uvo_kfdb_detect_loop_haloc", "uvo_kfdb_last_query", "uvo_kfdb_last_haloc", "uvo_kfdb_state", "uvo_kfdb_size",
@@ -309,6 +310,11 @@ def _load():
     lib.uvo_nav_bundle_adjuster_destroy.restype = None
     lib.uvo_nav_bundle_adjust.argtypes = [vp, vp, vp]
     lib.uvo_nav_bundle_adjuster_trace.argtypes = [vp, vp]
+    lib.uvo_essential_graph_create.argtypes = [vp, ci, ci, ci, ci, vp]
+    lib.uvo_essential_graph_destroy.argtypes = [vp]
+    lib.uvo_essential_graph_destroy.restype = None
+    lib.uvo_essential_graph_optimize.argtypes = [vp, vp, vp]
+    lib.uvo_essential_graph_trace.argtypes = [vp, vp]
     lib.uvo_sim3solver_set_create.argtypes = [vp, ci, ci, vp]
     lib.uvo_sim3solver_set_destroy.argtypes = [vp]
     lib.uvo_sim3solver_set_destroy.restype = None
@@ -2218,6 +2224,71 @@ class NavBundleAdjuster(_Adjuster):
     def trace(self):
         """Test tap: NavBaTrace of the last adjust() call."""
         return NavBaTrace(self._trace(NavBaTraceC()))
+
+
+class EssentialProblemC(ctypes.Structure):
+    """uvo_essential_problem."""
+    _fields_ = [("n_keyframes", ctypes.c_int32), ("n_edges", ctypes.c_int32), ("n_points", ctypes.c_int32), ("fixed", ctypes.c_int32),
+                ("Scw", ctypes.c_void_p), ("Scw_normal", ctypes.c_void_p), ("edge_i", ctypes.c_void_p), ("edge_j", ctypes.c_void_p),
+                ("edge_connection", ctypes.c_void_p), ("points", ctypes.c_void_p), ("point_ref", ctypes.c_void_p), ("n_iterations", ctypes.c_int32)]
+
+
+class EssentialResultC(ctypes.Structure):
+    """uvo_essential_result."""
+    _fields_ = [("Scw", ctypes.c_void_p), ("kf_Tcw", ctypes.c_void_p), ("points", ctypes.c_void_p), ("iterations", ctypes.c_int32),
+                ("n_trials", ctypes.c_int32), ("n_syncs", ctypes.c_int32), ("envelope_blocks", ctypes.c_int32)]
+
+
+class EssentialResult:
+    """One optimised graph: Scw float64[K, 8] (quaternion x y z w not normalised, t, s), kf_Tcw float32[K, 4, 4] = [R | t / s], points
+    float32[P, 3], iterations (linearisations), n_trials, n_syncs, envelope_blocks."""
+
+    def __init__(self, c, arrays):
+        self.Scw, self.kf_Tcw, self.points = arrays
+        self.iterations, self.n_trials, self.n_syncs, self.envelope_blocks = c.iterations, c.n_trials, c.n_syncs, c.envelope_blocks
+
+
+def essential_marshal(scene, n_iterations=None):
+    """A scene dict (Scw [K, 8], Scwn [K, 8] or absent: Scw, edge_i [E], edge_j [E], conn [E], points [P, 3], ref [P], fixed, n_iterations)
+    -> (EssentialProblemC, EssentialResultC, the result's arrays, what to keep alive)."""
+    f64, i32 = np.float64, np.int32
+    S = np.ascontiguousarray(scene["Scw"], f64).reshape(-1, 8)
+    Sn = np.ascontiguousarray(scene["Scwn"] if scene.get("Scwn") is not None else S, f64).reshape(-1, 8)
+    ei, ej = np.ascontiguousarray(scene["edge_i"], i32).reshape(-1), np.ascontiguousarray(scene["edge_j"], i32).reshape(-1)
+    conn = np.ascontiguousarray(scene["conn"], np.uint8).reshape(-1)
+    pts, ref = np.ascontiguousarray(scene["points"], np.float32).reshape(-1, 3), np.ascontiguousarray(scene["ref"], i32).reshape(-1)
+    K, E, P = len(S), len(ei), len(pts)
+    if len(Sn) != K or len(ej) != E or len(conn) != E or len(ref) != P:
+        raise ValueError("the arrays of the problem differ in length")
+    c = EssentialProblemC()
+    c.n_keyframes, c.n_edges, c.n_points, c.fixed = K, E, P, int(scene["fixed"])
+    c.Scw, c.Scw_normal, c.edge_i, c.edge_j, c.edge_connection = S.ctypes.data, Sn.ctypes.data, ei.ctypes.data, ej.ctypes.data, conn.ctypes.data
+    c.points, c.point_ref = pts.ctypes.data, ref.ctypes.data
+    c.n_iterations = int(scene.get("n_iterations", 20) if n_iterations is None else n_iterations)
+    out = [np.zeros((max(K, 1), 8)), np.zeros((max(K, 1), 4, 4), np.float32), np.zeros((max(P, 1), 3), np.float32)]
+    r = EssentialResultC()
+    r.Scw, r.kf_Tcw, r.points = out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data
+    return c, r, [out[0][:K], out[1][:K], out[2][:P]], (S, Sn, ei, ej, conn, pts, ref, out)
+
+
+class EssentialGraph(_Adjuster):
+    """Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:2409-2658) for a gathered graph on an ORBmatcher handle, the loop-closing
+    thread's stream: optimize() runs one graph, every phase a launch of its own, the Levenberg decision on the device, the system by a
+    block-envelope LDL^T in key-frame order.  `_api` exists so that the tests can drive another build through this class."""
+    _handle, _call = "uvo_essential_graph", "uvo_essential_graph_optimize"
+
+    def __init__(self, matcher, max_keyframes=2048, max_edges=16384, max_envelope_blocks=1 << 18, max_points=1 << 17, _api=None):
+        super().__init__(matcher, (max_keyframes, max_edges, max_envelope_blocks, max_points), _api)
+
+    def optimize(self, scene, n_iterations=None):
+        """scene: the dict essential_marshal() describes -> EssentialResult."""
+        c, r, arrays, keep = essential_marshal(scene, n_iterations)
+        self._adjust(c, r)
+        return EssentialResult(r, arrays)
+
+    def trace(self):
+        """Test tap: BaTrace of the last optimize() call (lin: chi2 per linearisation; trial: lambda, cur, tmp, scale, ok, accepted)."""
+        return BaTrace(self._trace(BaTraceC()))
 
 
 class InitializerResultC(ctypes.Structure):

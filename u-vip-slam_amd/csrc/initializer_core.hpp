@@ -393,11 +393,7 @@ SIM3_HD int check_rt_one(const WS& w, const float* R, const float* t, const Cam&
   return kCounted | (low ? kGood : 0);
 }
 
-// acos on [-1, 1] from IEEE operations: atan2(sqrt((1 - x)(1 + x)), x)
-SIM3_HD double acos_ieee(double x) {
-  if (!(x >= -1. && x <= 1.)) return (x - x) / (x - x) + (1. - 1.) / (x - x);  // NaN
-  return sim3::atan2_pos(sqrt((1. - x) * (1. + x)), x);
-}
+using sim3::acos_ieee;  // sim3_core.hpp: essential_core.hpp takes it from there too
 // :898 acos(c) * 180 / CV_PI [OCV-RECALL 5]
 SIM3_HD float parallax_deg(float c) {
   const float a = (float)acos_ieee((double)c);

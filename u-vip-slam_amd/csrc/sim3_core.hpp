@@ -139,6 +139,12 @@ SIM3_HD double atan2_pos(double y, double x) {
   return x >= 0. ? 0x1.921fb54442d18p+0 - (v - 0x1.1a62633145c07p-54) : 0x1.921fb54442d18p+0 + (v + 0x1.1a62633145c07p-54);
 }
 
+// acos on [-1, 1] from IEEE operations: atan2(sqrt((1 - x)(1 + x)), x)
+SIM3_HD double acos_ieee(double x) {
+  if (!(x >= -1. && x <= 1.)) return (x - x) / (x - x) + (1. - 1.) / (x - x);  // NaN
+  return atan2_pos(sqrt((1. - x) * (1. + x)), x);
+}
+
 // ---- cv::eigen of a symmetric 4 x 4 CV_32F matrix [OCV-RECALL 4] ---------------------------------------------------------------------
 PNP_HD float ocv_hypot(float a, float b) {
   a = fabsf(a), b = fabsf(b);
