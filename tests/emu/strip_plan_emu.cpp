@@ -36,6 +36,17 @@ extern "C" int emu_strip_plan_check(int w, int h, int rows_per_seg, int* items_o
   return 0;
 }
 
+// The plan itself, for the Python restatement of tests/fast_model.py: head = {nfull, nseg, items, sub[0], sub[1], x0[0], x0[1]}, then
+// (strip_x, seg, sub) of the first `cap` items as fast_strip_item decodes them.  Returns the number of items.
+extern "C" int emu_strip_plan_items(int w, int h, int rows_per_seg, int* head, int* items_out, int cap) {
+  using namespace uvo;
+  StripPlan P;
+  fast_strip_plan(w, h, rows_per_seg, P);
+  head[0] = P.nfull, head[1] = P.nseg, head[2] = P.items, head[3] = P.sub[0], head[4] = P.sub[1], head[5] = P.x0[0], head[6] = P.x0[1];
+  for (int item = 0; item < P.items && item < cap; ++item) fast_strip_item(P, item, items_out[3 * item], items_out[3 * item + 1], items_out[3 * item + 2]);
+  return P.items;
+}
+
 // xcd_contiguous must be a permutation of [0, total) that keeps the workgroups of one XCD (b % 8) in one contiguous range
 extern "C" int emu_xcd_contiguous_check(int total) {
   std::vector<int> seen(total, 0);

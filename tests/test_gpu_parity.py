@@ -6,6 +6,8 @@ import os
 import numpy as np
 import pytest
 
+from fast_cases import fast_mode_images as _fast_mode_images   # the frames of the FAST-mode tests, shared with tests/test_fast_model.py
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -109,29 +111,6 @@ def test_degenerate_images(uvo, oracle):
         kp_o, de_o = oe(img)
         _assert_same_features(kp_g, de_g, kp_o, de_o, name)
     ex.close()
-
-
-def _fast_mode_images(synth):
-    """Frames that put the per-cell fallback of src/ORBextractor.cc:792-799 in every state: no cell falls back (textured), all do (flat,
-    low contrast), some do (textured left half / low-contrast right half; a dim frame), cells whose only corners >= fastTh are
-    equal-score neighbours that suppress each other (so `FAST(cell, 20)` is empty although pixels score >= 20, and in the second
-    call those pixels still suppress their weaker neighbours), and dense noise."""
-    rng = np.random.default_rng(11)
-    H, W = 512, 640
-    tex = synth.make_frame(4242, W, H)
-    low = (rng.integers(0, 12, (H, W)) + 100).astype(np.uint8)
-    half = tex.copy()
-    half[:, W // 2:] = low[:, W // 2:]
-    dim = (tex.astype(np.float32) * 0.22 + 90).astype(np.uint8)   # contrast cut to a fifth: most corners score below 20
-    # pairs of identical bright 2x1 blobs on a flat background: both pixels of a pair get the same score and annihilate
-    ties = np.full((H, W), 100, np.uint8)
-    ties += rng.integers(0, 9, (H, W)).astype(np.uint8)           # weak corners (score >= 7) around them
-    for y in range(40, H - 40, 37):
-        for x in range(40, W - 40, 41):
-            ties[y, x] = ties[y, x + 1] = 190
-    noise = rng.integers(0, 256, (H, W), dtype=np.uint8)
-    flat = np.full((H, W), 77, np.uint8)
-    return (("textured", tex), ("lowcontrast", low), ("half", half), ("dim", dim), ("ties", ties), ("noise", noise), ("flat", flat))
 
 
 @pytest.mark.parametrize("mode", ["two_pass", "single_pass", "adaptive"])
