@@ -138,6 +138,51 @@ def test_capacity_edges(uvo, emu, klt):
         pset.close()
 
 
+@pytest.mark.parametrize("S,N", [(0, 10), (65, 10), (1, 3), (1, 16385)])
+def test_a_set_outside_1_to_64_solvers_of_4_to_16384_points_is_refused(uvo, klt, S, N):
+    with pytest.raises(uvo.UvoError) as ei:
+        uvo.PnPsolverSet(klt, S, N)
+    assert ei.value.code == uvo.UVO_E_BADARG and "1..64 solvers of 4..16384 points" in str(ei.value)
+
+
+def one_call(uvo, pset, ids, n_iterations, g):
+    """One iterate call with everything a session records of it."""
+    res = pset.iterate(ids, n_iterations, g)
+    infos = [pset.query(i) for i in ids]
+    return pc.Call(list(ids), n_iterations, res, g.state(), [pset.hypotheses(i) for i in ids],
+                   [(f.n, f.min_inliers, f.max_its, f.iterations, f.best_inliers) for f in infos])
+
+
+def test_refused_iterate_calls_leave_the_generator_the_solvers_and_the_next_call_alone(uvo, klt):
+    """No iterations, a mask shorter than n_matches, more hypotheses than the set has slots (max(mRansacMaxIts, 321) > 320 per solver: at
+    the only solver of a (1, 70) set, and at the second of a (2, 70) set, when the first's records are written already): each is
+    refused with its code and text, the caller's generator and mnIterations stay, and the call that follows equals, field for field,
+    tap for tap and in generator state, the same call on a set that saw none of them."""
+    p3d, p2d, sigma2, kp, nm, K, _, _ = psm.candidate(1, 20, 0.5)
+    pset, fresh, single = uvo.PnPsolverSet(klt, 2, 70), uvo.PnPsolverSet(klt, 2, 70), uvo.PnPsolverSet(klt, 1, 70)
+    try:
+        for p in (pset, fresh):
+            a, b = p.add(p3d, p2d, sigma2, kp, nm, K), p.add(p3d, p2d, sigma2, kp, nm, K)
+        assert single.add(p3d, p2d, sigma2, kp, nm, K) == a
+        g = uvo.GlibcRand(1)
+        slots = "more hypothesis slots than the set has (320 per solver)"
+        for p, ids, n_it, kw, code, text in ((pset, [a], 0, {}, uvo.UVO_E_BADARG, "n_iterations must be at least 1"),
+                                             (pset, [a], 5, dict(inliers_cap=nm - 1), uvo.UVO_E_CAPACITY, "inliers_cap is smaller"),
+                                             (single, [a], 321, {}, uvo.UVO_E_BADARG, slots),
+                                             (pset, [a, b], 321, {}, uvo.UVO_E_BADARG, slots)):
+            with pytest.raises(uvo.UvoError) as ei:
+                p.iterate(ids, n_it, g, **kw)
+            assert ei.value.code == code and text in str(ei.value), (ids, n_it, kw, str(ei.value))
+            assert g.state() == advanced(uvo, 0) and p.query(a).iterations == 0, (ids, n_it, kw)
+            assert all(len(p.hypotheses(i)[2]) == 0 for i in ids), (ids, n_it, kw)
+        x, y = one_call(uvo, pset, [a, b], 5, g), one_call(uvo, fresh, [a, b], 5, uvo.GlibcRand(1))
+        pc.assert_sessions_equal([x], [y], "after the refused calls")
+        assert x.result.status[0].tolist()[:1] == [1] and x.infos[0][3] > 0 and x.rng_state == advanced(uvo, x.result.draws)
+    finally:
+        for p in (pset, fresh, single):
+            p.close()
+
+
 def test_a_set_filled_to_capacity_equals_one_with_room_to_spare(uvo, emu, klt):
     """Both solvers of a (2, 65) set hold 65 points -- the last element of every array of the set's block is written and read, the inlier
     set spans two 64-bit words -- and the session equals, bit for bit, the one on an (8, 256) set, where every array lies elsewhere."""

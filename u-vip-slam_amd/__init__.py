@@ -1410,23 +1410,28 @@ class PnPsolverResult:
         self.status, self.inliers = status, inliers
 
 
-class PnPsolverSet:
-    """USLAM::PnPsolver for Tracking::Relocalisation (src/Tracking.cc:2415-2517): the solvers of all candidate key frames in one set on
-    a KLT handle, iterate() over a list of them as one device call.  `_api` / `_prefix` exist so that the tests' host build of the same
-    source can be driven through this very class."""
-    _prefix = "uvo_pnpsolver_"
+class _SolverSet:
+    """What PnPsolverSet and Sim3SolverSet share (csrc/solver_set.hpp behind both): a set made by `<_prefix>set_create` on a handle and
+    freed by `<_prefix>set_destroy`, and the one call that marshals status, mask and inliers_cap.  A subclass names `_prefix`, `_info`,
+    `_result_c` and `_result`.  `_api` / `_prefix` exist so that the tests' host build of the same source can be driven through the
+    very subclass; errors name the library's function (`_where`) either way."""
 
-    def __init__(self, klt, max_solvers, max_points, _api=None):
+    def __init__(self, handle, max_solvers, max_points, _api=None):
         self._api = _api if _api is not None else lib
-        self._klt = klt   # the set launches in the handle's stream: keep it alive
+        self._handle = handle   # the set launches in the handle's stream: keep it alive
         self._h = ctypes.c_void_p()
         self._n_matches = []
-        rc = self._f("set_create")(klt._h if klt is not None else None, max_solvers, max_points, ctypes.byref(self._h))
+        rc = self._f("set_create")(handle._h if handle is not None else None, max_solvers, max_points, ctypes.byref(self._h))
         if rc:
-            raise UvoError(rc, "uvo_pnpsolver_set_create")
+            raise UvoError(rc, self._where + "set_create")
 
     def _f(self, name):
         return getattr(self._api, self._prefix + name)
+
+    def _do(self, name, *args):
+        rc = self._f(name)(self._h, *args)
+        if rc:
+            raise UvoError(rc, self._where + name)
 
     def close(self):
         if getattr(self, "_h", None) and self._api is not None:
@@ -1436,10 +1441,51 @@ class PnPsolverSet:
     __del__ = close
 
     def clear(self):
-        rc = self._f("set_clear")(self._h)
-        if rc:
-            raise UvoError(rc, "uvo_pnpsolver_set_clear")
+        self._do("set_clear")
         self._n_matches = []
+
+    def _added(self, n_matches, *args):
+        sid = ctypes.c_int()
+        self._do("add", *args, ctypes.byref(sid))
+        self._n_matches.append(n_matches)
+        return sid.value
+
+    def query(self, sid):
+        info = self._info()
+        self._do("query", sid, ctypes.byref(info))
+        return info
+
+    def _call(self, name, ids, inliers_cap, *args):
+        status = np.zeros((len(ids), 3), np.int32)
+        cap = max([self._n_matches[i] for i in ids if 0 <= i < len(self._n_matches)] + [1]) if inliers_cap is None else int(inliers_cap)
+        mask = np.zeros(max(cap, 1), np.uint8)
+        res = self._result_c()
+        res.status, res.inliers, res.inliers_cap = status.ctypes.data, mask.ctypes.data, cap
+        rc = self._f(name)(self._h, *args, ctypes.byref(res))   # not through _do: one Python call less on the path that is timed
+        if rc:
+            raise UvoError(rc, self._where + name)
+        return self._result(res, status, mask[:self._n_matches[res.solver]].copy() if res.returned >= 0 else mask[:0].copy())
+
+    def iterate(self, ids, n_iterations, rng, inliers_cap=None):
+        """iterate(n_iterations) on each id in order until one returns; rng (GlibcRand) is advanced in place -> the subclass's result."""
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        return self._call("iterate", ids, inliers_cap, _ptr(ids), len(ids), int(n_iterations), ctypes.byref(rng))
+
+    def _tap(self, sid, cap, *arrays):
+        """The arrays of a test tap, filled by `<_prefix>hypotheses` and cut to the hypotheses `sid` consumed in the last iterate call."""
+        n = ctypes.c_int()
+        self._do("hypotheses", sid, *(_ptr(a) for a in arrays), cap, ctypes.byref(n))
+        return tuple(a[:n.value].copy() for a in arrays)
+
+
+class PnPsolverSet(_SolverSet):
+    """USLAM::PnPsolver for Tracking::Relocalisation (src/Tracking.cc:2415-2517): the solvers of all candidate key frames in one set on
+    a KLT handle, iterate() over a list of them as one device call -> PnPsolverResult."""
+    _prefix = _where = "uvo_pnpsolver_"
+    _info, _result_c, _result = PnPsolverInfo, PnPsolverResultC, PnPsolverResult
+
+    def __init__(self, klt, max_solvers, max_points, _api=None):
+        super().__init__(klt, max_solvers, max_points, _api)
 
     def add(self, p3d, p2d, sigma2, kp_index=None, n_matches=None, K=(1.0, 1.0, 0.0, 0.0), params=None):
         """PnPsolver(F, vpMapPointMatches) + SetRansacParameters -> solver id.  kp_index defaults to 0..n-1, n_matches to n."""
@@ -1451,32 +1497,7 @@ class PnPsolverSet:
             raise ValueError("p3d, p2d, sigma2 and kp_index differ in length")
         nm = len(a) if n_matches is None else int(n_matches)
         prm = params if params is not None else PnPsolverParams()
-        sid = ctypes.c_int()
-        rc = self._f("add")(self._h, _ptr(a), _ptr(b), _ptr(sg), _ptr(kp), len(a), nm, K[0], K[1], K[2], K[3], ctypes.byref(prm), ctypes.byref(sid))
-        if rc:
-            raise UvoError(rc, "uvo_pnpsolver_add")
-        self._n_matches.append(nm)
-        return sid.value
-
-    def query(self, sid):
-        info = PnPsolverInfo()
-        rc = self._f("query")(self._h, sid, ctypes.byref(info))
-        if rc:
-            raise UvoError(rc, "uvo_pnpsolver_query")
-        return info
-
-    def iterate(self, ids, n_iterations, rng):
-        """iterate(n_iterations) on each id in order until one returns a pose; rng (GlibcRand) is advanced in place -> PnPsolverResult."""
-        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
-        status = np.zeros((len(ids), 3), np.int32)
-        cap = max([self._n_matches[i] for i in ids if 0 <= i < len(self._n_matches)] + [1])
-        mask = np.zeros(cap, np.uint8)
-        res = PnPsolverResultC()
-        res.status, res.inliers, res.inliers_cap = status.ctypes.data, mask.ctypes.data, cap
-        rc = self._f("iterate")(self._h, _ptr(ids), len(ids), int(n_iterations), ctypes.byref(rng), ctypes.byref(res))
-        if rc:
-            raise UvoError(rc, "uvo_pnpsolver_iterate")
-        return PnPsolverResult(res, status, mask[:self._n_matches[res.solver]].copy() if res.returned >= 0 else mask[:0].copy())
+        return self._added(nm, _ptr(a), _ptr(b), _ptr(sg), _ptr(kp), len(a), nm, K[0], K[1], K[2], K[3], ctypes.byref(prm))
 
     def find(self, sid, rng):
         """PnPsolver::find: iterate(mRansacMaxIts)."""
@@ -1484,11 +1505,7 @@ class PnPsolverSet:
 
     def hypotheses(self, sid, min_set=4, cap=1024):
         """Test tap: (subsets int32[h, min_set], poses float64[h, 12], counts int32[h]) solver `sid` consumed in the last iterate call."""
-        sub, poses, cnt, n = np.zeros((cap, min_set), np.int32), np.zeros((cap, 12)), np.zeros(cap, np.int32), ctypes.c_int()
-        rc = self._f("hypotheses")(self._h, sid, _ptr(sub), _ptr(poses), _ptr(cnt), cap, ctypes.byref(n))
-        if rc:
-            raise UvoError(rc, "uvo_pnpsolver_hypotheses")
-        return sub[:n.value].copy(), poses[:n.value].copy(), cnt[:n.value].copy()
+        return self._tap(sid, cap, np.zeros((cap, min_set), np.int32), np.zeros((cap, 12)), np.zeros(cap, np.int32))
 
 
 class PoseProblemC(ctypes.Structure):
@@ -1786,36 +1803,14 @@ class Sim3SolverResult:
         self.status, self.inliers = status, inliers
 
 
-class Sim3SolverSet:
+class Sim3SolverSet(_SolverSet):
     """USLAM::Sim3Solver for LoopClosing::ComputeSim3 (src/LoopClosing.cc:373-479): the solvers of all loop candidates in one set on an
-    ORBmatcher handle, iterate() over a list of them as one device call.  `_api` / `_prefix` exist so that the tests' host build of the
-    same source can be driven through this very class."""
-    _prefix = "uvo_sim3solver_"
+    ORBmatcher handle, iterate() over a list of them as one device call -> Sim3SolverResult."""
+    _prefix = _where = "uvo_sim3solver_"
+    _info, _result_c, _result = Sim3SolverInfo, Sim3SolverResultC, Sim3SolverResult
 
     def __init__(self, matcher, max_solvers, max_points, _api=None):
-        self._api = _api if _api is not None else lib
-        self._matcher = matcher   # the set launches in the handle's stream: keep it alive
-        self._h = ctypes.c_void_p()
-        self._n_matches = []
-        rc = self._f("set_create")(matcher._h if matcher is not None else None, max_solvers, max_points, ctypes.byref(self._h))
-        if rc:
-            raise UvoError(rc, "uvo_sim3solver_set_create")
-
-    def _f(self, name):
-        return getattr(self._api, self._prefix + name)
-
-    def close(self):
-        if getattr(self, "_h", None) and self._api is not None:
-            self._f("set_destroy")(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def clear(self):
-        rc = self._f("set_clear")(self._h)
-        if rc:
-            raise UvoError(rc, "uvo_sim3solver_set_clear")
-        self._n_matches = []
+        super().__init__(matcher, max_solvers, max_points, _api)
 
     def add(self, x1w, x2w, sigma2_1, sigma2_2, index1, n_matches, kf1, kf2, params=None):
         """Sim3Solver(pKF1, pKF2, vpMatched12) + SetRansacParameters -> solver id.  kf1, kf2: (Rcw, tcw, (fx, fy, cx, cy)) or
@@ -1831,41 +1826,10 @@ class Sim3SolverSet:
         k1 = kf1 if isinstance(kf1, Sim3KeyFrame) else Sim3KeyFrame.make(*kf1)
         k2 = kf2 if isinstance(kf2, Sim3KeyFrame) else Sim3KeyFrame.make(*kf2)
         prm = params if params is not None else Sim3SolverParams()
-        sid = ctypes.c_int()
-        rc = self._f("add")(self._h, _ptr(a), _ptr(b), _ptr(s1), _ptr(s2), _ptr(ix), len(a), nm, ctypes.byref(k1), ctypes.byref(k2), ctypes.byref(prm),
-                            ctypes.byref(sid))
-        if rc:
-            raise UvoError(rc, "uvo_sim3solver_add")
-        self._n_matches.append(nm)
-        return sid.value
+        return self._added(nm, _ptr(a), _ptr(b), _ptr(s1), _ptr(s2), _ptr(ix), len(a), nm, ctypes.byref(k1), ctypes.byref(k2), ctypes.byref(prm))
 
     def set_ransac_parameters(self, sid, params):
-        rc = self._f("set_ransac_parameters")(self._h, sid, ctypes.byref(params))
-        if rc:
-            raise UvoError(rc, "uvo_sim3solver_set_ransac_parameters")
-
-    def query(self, sid):
-        info = Sim3SolverInfo()
-        rc = self._f("query")(self._h, sid, ctypes.byref(info))
-        if rc:
-            raise UvoError(rc, "uvo_sim3solver_query")
-        return info
-
-    def _call(self, name, ids, inliers_cap, *args):
-        status = np.zeros((len(ids), 3), np.int32)
-        cap = max([self._n_matches[i] for i in ids if 0 <= i < len(self._n_matches)] + [1]) if inliers_cap is None else int(inliers_cap)
-        mask = np.zeros(max(cap, 1), np.uint8)
-        res = Sim3SolverResultC()
-        res.status, res.inliers, res.inliers_cap = status.ctypes.data, mask.ctypes.data, cap
-        rc = self._f(name)(self._h, *args, ctypes.byref(res))
-        if rc:
-            raise UvoError(rc, "uvo_sim3solver_" + name)
-        return Sim3SolverResult(res, status, mask[:self._n_matches[res.solver]].copy() if res.returned >= 0 else mask[:0].copy())
-
-    def iterate(self, ids, n_iterations, rng, inliers_cap=None):
-        """iterate(n_iterations) on each id in order until one returns a transform; rng (GlibcRand) is advanced in place."""
-        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
-        return self._call("iterate", ids, inliers_cap, _ptr(ids), len(ids), int(n_iterations), ctypes.byref(rng))
+        self._do("set_ransac_parameters", sid, ctypes.byref(params))
 
     def find(self, sid, rng):
         """Sim3Solver::find: iterate(mRansacMaxIts)."""
@@ -1873,12 +1837,7 @@ class Sim3SolverSet:
 
     def hypotheses(self, sid, cap=1024):
         """Test tap: (subsets int32[h, 3], T12 float32[h, 16], T21 float32[h, 16], counts int32[h]) of the last iterate call."""
-        sub, t12, t21 = np.zeros((cap, 3), np.int32), np.zeros((cap, 16), np.float32), np.zeros((cap, 16), np.float32)
-        cnt, n = np.zeros(cap, np.int32), ctypes.c_int()
-        rc = self._f("hypotheses")(self._h, sid, _ptr(sub), _ptr(t12), _ptr(t21), _ptr(cnt), cap, ctypes.byref(n))
-        if rc:
-            raise UvoError(rc, "uvo_sim3solver_hypotheses")
-        return sub[:n.value].copy(), t12[:n.value].copy(), t21[:n.value].copy(), cnt[:n.value].copy()
+        return self._tap(sid, cap, np.zeros((cap, 3), np.int32), np.zeros((cap, 16), np.float32), np.zeros((cap, 16), np.float32), np.zeros(cap, np.int32))
 
 
 class Sim3OptProblemC(ctypes.Structure):

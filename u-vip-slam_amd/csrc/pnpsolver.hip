@@ -2,7 +2,8 @@
 // call.  All arithmetic is pnpsolver_core.hpp / epnp_core.hpp, shared with the host build tests/emu/pnpsolver_emu.cpp; this file
 // decides which lane computes which scalar.  What makes it one call: the iterations a solver runs unless it returns are known before
 // anything is evaluated (max(max_its - mnIterations, n_iterations), the loop condition being an OR), so the host draws every subset of
-// the call from the caller's generator state up front, and the stream position of each solver is a prefix sum.
+// the call from the caller's generator state up front, and the stream position of each solver is a prefix sum.  That host side -- the
+// set, the exchange, iterate's walk -- is solver_set.hpp, shared with sim3solver.hip; below the kernels stands what is the PnPsolver's.
 //
 // Three launches in the uvo_klt handle's stream, all scratch sized at uvo_pnpsolver_set_create:
 //   k_pnps_hypotheses : EPnP on min_set points, one lane per (solver, hypothesis), eight lanes per workgroup with their 589-double
@@ -20,8 +21,8 @@
 #include <cstring>
 #include <vector>
 
-#include "devmem.hpp"
 #include "pnpsolver.hpp"
+#include "solver_set.hpp"
 
 namespace uvo {
 
@@ -180,32 +181,55 @@ __global__ __launch_bounds__(256) void k_pnps_finish(PnpsDev D) {
 using namespace uvo;
 
 namespace {
-struct Solver {
-  int n = 0, n_matches = 0;
+struct Solver : SetSolver {
   pnps::Params params;
   pnps::Derived d;
   double fu = 0, fv = 0, uc = 0, vc = 0;
-  pnps::State st = {0, 0};
   int parity = 0;
-  std::vector<int32_t> kp_index;
-  int tap_off = 0, tap_n = 0;  // the hypotheses it consumed in the last iterate call
 };
 }  // namespace
 
-struct uvo_pnpsolver_set {
+struct uvo_pnpsolver_set : SolverSet<PnpsCall, PnpsResult> {
   uvo_klt* klt = nullptr;
-  hipStream_t stream = nullptr;
-  int device = 0, max_solvers = 0, max_points = 0, words = 0, total = 0;
-  DevMem mem;  // owns D's block and the page-locked mirrors of its two exchanges
   PnpsDev D;
   float *p3d = nullptr, *p2d = nullptr, *max_err = nullptr;  // writable views of D's
-  PnpsCall* h_call = nullptr;  // the upload: call records, then hypothesis records
-  int32_t* h_hyp = nullptr;
-  PnpsResult* h_res = nullptr;  // the download: result records, then the returned sets
-  uint64_t* h_om = nullptr;
   std::vector<Solver> solvers;
-  std::vector<int32_t> avail;  // draw_subset's slots
-  std::vector<char> seen;      // per solver: listed in the current call
+
+  // what solver_set.hpp asks of a family
+  static constexpr int kMaxSolvers = kPnpsMaxSolvers, kMinPoints = pnps::kMinSetLo, kMaxPoints = kPnpsMaxPoints, kHypPerSolver = kPnpsHypPerSolver;
+  static constexpr int kSubsetStride = kPnpsSubsetStride;
+  static constexpr const char* kRangeText = "PnPsolver set: 1..64 solvers of 4..16384 points";
+  static constexpr const char* kNoMemText = "PnPsolver set allocation failed";
+  static constexpr const char* kFullText = "the PnPsolver set is full";
+  void arrays(Carve& c, bool scratch) {
+    const size_t S = (size_t)max_solvers, N = (size_t)max_points, W = (size_t)words, T = (size_t)total;
+    if (!scratch) c.take(p3d, S * N * 3).take(p2d, S * N * 2).take(max_err, S * N).take(D.best_mask, S * 2 * W).take(D.best_pose, S * 2 * 12);
+    else c.take(D.poses, T * 12).take(D.counts, T).take(D.masks, T * W).take(D.list, S * N);
+  }
+  static int min_set(const Solver& v) { return v.params.min_set; }
+  // the loop condition is an OR; with fewer points than nMinInliers: bNoMore at once, nothing drawn
+  static int plan(const Solver& v, int n_iterations) { return v.n < v.d.min_inliers ? 0 : pnps::iterations_ahead(v.iterations, v.d.max_its, n_iterations); }
+  static PnpsCall call(int id, const Solver& v, int off, int K, int n_iterations) {
+    return PnpsCall{id, v.n, v.params.min_set, v.d.min_inliers, v.d.max_its, v.iterations, v.best_count, v.parity, off, K, n_iterations, 0, v.fu, v.fv, v.uc, v.vc};
+  }
+  void launch(int n_ids, int total) const {  // no profiler scope: a uvo_klt handle has no profiler
+    hipLaunchKernelGGL(k_pnps_hypotheses, dim3((total + kPnpsHypLanes - 1) / kPnpsHypLanes), dim3(kPnpsHypLanes), 0, stream, D, total);
+    hipLaunchKernelGGL(k_pnps_score, dim3(total), dim3(256), 0, stream, D);
+    hipLaunchKernelGGL(k_pnps_finish, dim3(n_ids), dim3(256), 0, stream, D);
+  }
+  static int idle_no_more(const Solver&) { return 1; }
+  static bool adopt(Solver& v, const PnpsResult& r, uvo_pnpsolver_result* result) {
+    v.parity ^= 1;  // k_pnps_finish wrote the other copy of the best set and pose
+    if (r.returned == pnps::kNone) return false;
+    result->refined = r.returned == pnps::kRefined ? 1 : 0;
+    float* T = result->Tcw;
+    for (int a = 0; a < 3; ++a) {
+      for (int b = 0; b < 3; ++b) T[4 * a + b] = (float)r.pose[3 * a + b];
+      T[4 * a + 3] = (float)r.pose[9 + a];
+    }
+    T[15] = 1.f;
+    return true;
+  }
 };
 
 extern "C" {
@@ -217,58 +241,27 @@ void uvo_glibc_srand(uvo_glibc_rand* g, uint32_t seed) {
 
 int32_t uvo_glibc_rand_next(uvo_glibc_rand* g) { return g ? reinterpret_cast<pnps::GlibcRand*>(g)->next() : 0; }
 
-void uvo_pnpsolver_set_destroy(uvo_pnpsolver_set* s) {
-  if (!s) return;
-  hipSetDevice(s->device);
-  if (s->stream) hipStreamSynchronize(s->stream);
-  s->mem.release_all();
-  delete s;
-}
+void uvo_pnpsolver_set_destroy(uvo_pnpsolver_set* s) { set_destroy(s); }
 
 int uvo_pnpsolver_set_create(uvo_klt* k, int max_solvers, int max_points, uvo_pnpsolver_set** out) {
   if (!k || !out) return fail(UVO_E_BADARG, "null pointer");
   *out = nullptr;
-  if (max_solvers < 1 || max_solvers > kPnpsMaxSolvers || max_points < pnps::kMinSetLo || max_points > kPnpsMaxPoints)
-    return fail(UVO_E_BADARG, "PnPsolver set: 1..64 solvers of 4..16384 points");
-  uvo_pnpsolver_set* s = new uvo_pnpsolver_set();
-  s->klt = k, s->stream = klt_stream(k), s->device = klt_device(k);
-  s->max_solvers = max_solvers, s->max_points = max_points, s->words = (max_points + 63) / 64, s->total = max_solvers * kPnpsHypPerSolver;
-  const size_t S = (size_t)max_solvers, N = (size_t)max_points, W = (size_t)s->words, T = (size_t)s->total;
+  uvo_pnpsolver_set* s = nullptr;
+  RC(set_create(klt_device(k), klt_stream(k), max_solvers, max_points, &s));
+  s->klt = k;
   PnpsDev& D = s->D;
   D.max_points = max_points, D.words = s->words;
-  // each exchange is one copy: its two arrays are adjacent, on the device and in the mirror
-  auto upload = [&](Carve& c, auto*& call, auto*& hyp) { c.take(call, S).take(hyp, T * kPnpsSubsetStride, alignof(int32_t)); };
-  auto download = [&](Carve& c, auto*& res, auto*& om) { c.take(res, S).take(om, S * W, alignof(uint64_t)); };
-  int rc = hipSetDevice(s->device) == hipSuccess ? UVO_OK : fail(UVO_E_NOMEM, "PnPsolver set allocation failed");
-  if (!rc) rc = alloc_carved(s->mem, [&](Carve& c) {
-    c.take(s->p3d, S * N * 3).take(s->p2d, S * N * 2).take(s->max_err, S * N).take(D.best_mask, S * 2 * W).take(D.best_pose, S * 2 * 12);
-    upload(c, D.call, D.hyp);
-    c.take(D.poses, T * 12).take(D.counts, T).take(D.masks, T * W).take(D.list, S * N);
-    download(c, D.result, D.out_mask);
-  });
-  if (!rc) rc = alloc_carved(s->mem, [&](Carve& c) { upload(c, s->h_call, s->h_hyp); }, true);
-  if (!rc) rc = alloc_carved(s->mem, [&](Carve& c) { download(c, s->h_res, s->h_om); }, true);
-  if (rc) return uvo_pnpsolver_set_destroy(s), rc;
   D.p3d = s->p3d, D.p2d = s->p2d, D.max_err = s->max_err;
-  s->avail.resize(N);
-  s->seen.resize(S);
-  s->solvers.reserve(S);
+  D.call = s->d_call, D.hyp = s->d_sub, D.result = s->d_res, D.out_mask = s->d_om;
   *out = s;
   return UVO_OK;
 }
 
-int uvo_pnpsolver_set_clear(uvo_pnpsolver_set* s) {
-  if (!s) return fail(UVO_E_BADARG, "null handle");
-  s->solvers.clear();
-  return UVO_OK;
-}
+int uvo_pnpsolver_set_clear(uvo_pnpsolver_set* s) { return set_clear(s); }
 
 int uvo_pnpsolver_add(uvo_pnpsolver_set* s, const float* p3d, const float* p2d, const float* sigma2, const int32_t* kp_index, int n, int n_matches,
                       float fx, float fy, float cx, float cy, const uvo_pnpsolver_params* params, int* id) {
-  if (!s || !params || !id) return fail(UVO_E_BADARG, "null pointer");
-  if (n < 0 || n > s->max_points || n_matches < n) return fail(UVO_E_BADARG, "point count outside 0..max_points, or more points than matches");
-  if (n > 0 && (!p3d || !p2d || !sigma2 || !kp_index)) return fail(UVO_E_BADARG, "null pointer");
-  if ((int)s->solvers.size() >= s->max_solvers) return fail(UVO_E_BADARG, "the PnPsolver set is full");
+  RC(add_check(s, params && id, n, n_matches, p3d && p2d && sigma2 && kp_index));
   const uvo_pnpsolver_params& q = *params;
   if (!(q.probability > 0. && q.probability < 1.) || !(q.epsilon >= 0.f && q.epsilon <= 1.f) || !(q.th2 >= 0.f) || !(fx == fx) || !(fy == fy) ||
       !(cx == cx) || !(cy == cy))
@@ -282,11 +275,10 @@ int uvo_pnpsolver_add(uvo_pnpsolver_set* s, const float* p3d, const float* p2d, 
   v.params = pnps::Params{q.probability, q.min_inliers, q.max_iterations, q.min_set, q.epsilon, q.th2};
   v.d = n > 0 ? pnps::derive_params(n, v.params) : pnps::Derived{0, q.min_inliers > q.min_set ? q.min_inliers : q.min_set, 1};
   v.fu = fx, v.fv = fy, v.uc = cx, v.vc = cy;
-  v.kp_index.assign(kp_index, kp_index + n);
-  const int sid = (int)s->solvers.size();
+  v.index.assign(kp_index, kp_index + n);
   if (n > 0) {
     UVO_HIP_CHECK(hipSetDevice(s->device));
-    const size_t N = (size_t)s->max_points;
+    const size_t N = (size_t)s->max_points, sid = s->solvers.size();
     std::vector<float> me(n);
     for (int i = 0; i < n; ++i) me[i] = sigma2[i] * q.th2;  // mvMaxError, in float
     UVO_HIP_CHECK(hipMemcpyAsync(s->p3d + sid * N * 3, p3d, (size_t)n * 12, hipMemcpyHostToDevice, s->stream));
@@ -294,124 +286,27 @@ int uvo_pnpsolver_add(uvo_pnpsolver_set* s, const float* p3d, const float* p2d, 
     UVO_HIP_CHECK(hipMemcpyAsync(s->max_err + sid * N, me.data(), (size_t)n * 4, hipMemcpyHostToDevice, s->stream));
     UVO_HIP_CHECK(hipStreamSynchronize(s->stream));  // the sources are the caller's pageable memory and a local
   }
-  s->solvers.push_back(std::move(v));
-  *id = sid;
-  return UVO_OK;
+  return add_finish(s, v, id);
 }
 
 int uvo_pnpsolver_query(uvo_pnpsolver_set* s, int id, uvo_pnpsolver_info* info) {
-  if (!s || !info) return fail(UVO_E_BADARG, "null pointer");
-  if (id < 0 || id >= (int)s->solvers.size()) return fail(UVO_E_BADARG, "no such solver");
+  RC(solver_check(s, info != nullptr, id));
   const Solver& v = s->solvers[id];
-  *info = uvo_pnpsolver_info{v.n, v.d.min_inliers, v.d.max_its, v.st.iterations, v.st.best_count};
+  *info = uvo_pnpsolver_info{v.n, v.d.min_inliers, v.d.max_its, v.iterations, v.best_count};
   return UVO_OK;
 }
 
 int uvo_pnpsolver_iterate(uvo_pnpsolver_set* s, const int32_t* ids, int n_ids, int n_iterations, uvo_glibc_rand* rng, uvo_pnpsolver_result* result) {
-  if (!s || !rng || !result || (n_ids > 0 && !ids)) return fail(UVO_E_BADARG, "null pointer");
-  if (n_ids < 0 || n_ids > s->max_solvers) return fail(UVO_E_BADARG, "more ids than the set has solvers");
-  if (n_iterations < 1) return fail(UVO_E_BADARG, "n_iterations must be at least 1");
-  uvo_pnpsolver_status* status = result->status;
-  uint8_t* mask_out = result->inliers;
-  result->returned = -1, result->solver = -1, result->n_inliers = 0, result->refined = 0, result->draws = 0;
-  std::fill(result->Tcw, result->Tcw + 16, 0.f);
-  std::vector<char>& seen = s->seen;
-  std::fill(seen.begin(), seen.end(), 0);
-  for (int j = 0; j < n_ids; ++j) {
-    if (ids[j] < 0 || ids[j] >= (int)s->solvers.size()) return fail(UVO_E_BADARG, "no such solver");
-    if (seen[ids[j]]) return fail(UVO_E_BADARG, "a solver is listed twice in one iterate call");
-    seen[ids[j]] = 1;
-    if (mask_out && result->inliers_cap < s->solvers[ids[j]].n_matches)
-      return fail(UVO_E_CAPACITY, "inliers_cap is smaller than a listed solver's n_matches");
-  }
-  for (Solver& v : s->solvers) v.tap_off = v.tap_n = 0;
-  if (status)
-    for (int j = 0; j < n_ids; ++j) status[j] = uvo_pnpsolver_status{0, 0, s->solvers[ids[j]].st.iterations};
-  // every subset of the call, from a copy of the caller's state: the stream position of a solver is the prefix sum of what the
-  // solvers in front of it run
-  pnps::GlibcRand g;
-  std::memcpy(&g, rng, sizeof g);
-  PnpsCall* call = s->h_call;
-  int32_t* hyp = s->h_hyp;
-  int total = 0;
-  for (int j = 0; j < n_ids; ++j) {
-    const Solver& v = s->solvers[ids[j]];
-    const int K = v.n < v.d.min_inliers ? 0 : pnps::iterations_ahead(v.st.iterations, v.d.max_its, n_iterations);
-    if (total + K > s->total) return fail(UVO_E_BADARG, "the call needs more hypothesis slots than the set has (320 per solver)");
-    call[j] = PnpsCall{ids[j], v.n, v.params.min_set, v.d.min_inliers, v.d.max_its, v.st.iterations, v.st.best_count, v.parity, total, K, n_iterations, 0,
-                       v.fu, v.fv, v.uc, v.vc};
-    for (int h = 0; h < K; ++h) {
-      int32_t* rec = hyp + (size_t)(total + h) * kPnpsSubsetStride;
-      rec[0] = j;
-      for (int e = 1; e < kPnpsSubsetStride; ++e) rec[e] = 0;
-      pnps::draw_subset(g, v.n, v.params.min_set, s->avail.data(), rec + 1);
-    }
-    total += K;
-  }
-  const PnpsResult* res = s->h_res;
-  const size_t W = (size_t)s->words;
-  if (total > 0) {
-    UVO_HIP_CHECK(hipSetDevice(s->device));
-    hipStream_t st = s->stream;
-    UVO_HIP_CHECK(hipMemcpyAsync(const_cast<PnpsCall*>(s->D.call), call, (size_t)s->max_solvers * sizeof(PnpsCall) + (size_t)total * kPnpsSubsetStride * 4,
-                                 hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_pnps_hypotheses, dim3((total + kPnpsHypLanes - 1) / kPnpsHypLanes), dim3(kPnpsHypLanes), 0, st, s->D, total);
-    hipLaunchKernelGGL(k_pnps_score, dim3(total), dim3(256), 0, st, s->D);
-    hipLaunchKernelGGL(k_pnps_finish, dim3(n_ids), dim3(256), 0, st, s->D);
-    UVO_HIP_CHECK(hipGetLastError());
-    // result records of all solver slots, then the sets of the listed ones: adjacent on the device
-    UVO_HIP_CHECK(hipMemcpyAsync(s->h_res, s->D.result, (size_t)s->max_solvers * sizeof(PnpsResult) + (size_t)n_ids * W * 8, hipMemcpyDeviceToHost, st));
-    UVO_HIP_CHECK(hipStreamSynchronize(st));
-  }
-  int draws = 0;
-  for (int j = 0; j < n_ids; ++j) {
-    Solver& v = s->solvers[ids[j]];
-    if (call[j].hyp_n == 0) {  // fewer points than nMinInliers: bNoMore at once, nothing drawn (n_iterations >= 1: every other solver has iterations to run)
-      if (status) status[j] = uvo_pnpsolver_status{1, 1, v.st.iterations};
-      continue;
-    }
-    const PnpsResult& r = res[j];
-    v.st.iterations += r.performed, v.st.best_count = r.best_count, v.parity ^= 1;
-    v.tap_off = call[j].hyp_off, v.tap_n = r.performed;
-    draws += r.performed * v.params.min_set;
-    if (status) status[j] = uvo_pnpsolver_status{1, r.no_more, v.st.iterations};
-    if (r.returned == pnps::kNone) continue;
-    result->returned = j, result->solver = ids[j], result->n_inliers = r.inliers, result->refined = r.returned == pnps::kRefined ? 1 : 0;
-    float* T = result->Tcw;
-    for (int a = 0; a < 3; ++a) {
-      for (int b = 0; b < 3; ++b) T[4 * a + b] = (float)r.pose[3 * a + b];
-      T[4 * a + 3] = (float)r.pose[9 + a];
-    }
-    T[15] = 1.f;
-    if (mask_out) {
-      std::fill(mask_out, mask_out + v.n_matches, (uint8_t)0);
-      const uint64_t* words = s->h_om + (size_t)j * W;
-      for (int i = 0; i < v.n; ++i)
-        if (words[i >> 6] >> (i & 63) & 1) mask_out[v.kp_index[i]] = 1;
-    }
-    break;
-  }
-  result->draws = (uint32_t)draws;  // the caller's state moves to where rand() would stand after the iterations actually performed
-  pnps::GlibcRand* gr = reinterpret_cast<pnps::GlibcRand*>(rng);
-  for (int d = 0; d < draws; ++d) (void)gr->next();
-  return UVO_OK;
+  return set_iterate(s, ids, n_ids, n_iterations, rng, result);
 }
 
 int uvo_pnpsolver_hypotheses(uvo_pnpsolver_set* s, int id, int32_t* subsets, double* poses, int32_t* counts, int cap, int* n) {
-  if (!s || !n) return fail(UVO_E_BADARG, "null pointer");
-  if (id < 0 || id >= (int)s->solvers.size()) return fail(UVO_E_BADARG, "no such solver");
-  if (cap < 0) return fail(UVO_E_BADARG, "negative capacity");
-  const Solver& v = s->solvers[id];
-  const int m = cap < v.tap_n ? cap : v.tap_n;
-  if (m > 0 && (!subsets || !poses || !counts)) return fail(UVO_E_BADARG, "null pointer");
-  *n = m;
-  if (m == 0) return UVO_OK;
-  const int32_t* hyp = s->h_hyp;  // the subsets were drawn on the host
-  for (int h = 0; h < m; ++h)
-    for (int e = 0; e < v.params.min_set; ++e) subsets[h * v.params.min_set + e] = hyp[(size_t)(v.tap_off + h) * kPnpsSubsetStride + 1 + e];
+  RC(tap_subsets(s, id, subsets, poses && counts, cap, n));
+  if (*n == 0) return UVO_OK;
+  const int off = s->solvers[id].tap_off;
   UVO_HIP_CHECK(hipSetDevice(s->device));
-  UVO_HIP_CHECK(hipMemcpy(poses, s->D.poses + (size_t)v.tap_off * 12, (size_t)m * 96, hipMemcpyDeviceToHost));
-  UVO_HIP_CHECK(hipMemcpy(counts, s->D.counts + v.tap_off, (size_t)m * 4, hipMemcpyDeviceToHost));
+  UVO_HIP_CHECK(hipMemcpy(poses, s->D.poses + (size_t)off * 12, (size_t)*n * 96, hipMemcpyDeviceToHost));
+  UVO_HIP_CHECK(hipMemcpy(counts, s->D.counts + off, (size_t)*n * 4, hipMemcpyDeviceToHost));
   return UVO_OK;
 }
 

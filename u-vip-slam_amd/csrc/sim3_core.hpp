@@ -1,8 +1,8 @@
 // Sim3Solver (src/Sim3Solver.cc of the reference: the RANSAC around Horn's closed form that LoopClosing::ComputeSim3 runs per loop
 // candidate) as plain C++.  sim3solver.hip runs this on the device, tests/emu/sim3solver_emu.cpp on the host; the two are held to each
 // other bit for bit under the rules of epnp_core.hpp's header: IEEE + - * / sqrt and fabs only, no contraction, every lane owns whole
-// scalars, no reduction tree over floating-point values.  The generator and the subset draw are pnps::GlibcRand / pnps::draw_subset at
-// a minimal set of 3.
+// scalars, no reduction tree over floating-point values.  The generator and the subset draw are glibc_rand.hpp's pnps::GlibcRand /
+// pnps::draw_subset at a minimal set of 3.
 //
 // computeT needs atan2, sin and cos in double, which are not shared-source functions.  atan2_pos and sincos below are built from IEEE
 // operations only (two-part constants, Taylor polynomials on a reduced range); they do not reproduce libm's bits, they are accurate to
@@ -26,7 +26,10 @@
 //   8. Project: invz = 1 / z, x * invz and fx * x + cx are float; dist.dot(dist) is a double narrowed to the float err.
 // derive_max_its uses pow / log / ceil and is HOST ONLY, as pnps::derive_params is.
 #pragma once
-#include "pnpsolver_core.hpp"
+#include <float.h>
+#include <math.h>
+
+#include "glibc_rand.hpp"
 
 #if defined(__HIPCC__)
 #define SIM3_HD __host__ __device__ __forceinline__  // outputs through pointers must not force the caller's locals into memory

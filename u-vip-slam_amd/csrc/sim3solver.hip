@@ -2,7 +2,8 @@
 // one call.  All arithmetic is sim3_core.hpp, shared with the host build tests/emu/sim3solver_emu.cpp; this file decides which lane
 // computes which scalar.  What makes it one call: iterate's loop condition is an AND, so a solver runs min(n_iterations, max_its -
 // mnIterations) iterations unless it returns; the host draws every subset of the call from the caller's generator state up front, and
-// the stream position of each solver is a prefix sum.
+// the stream position of each solver is a prefix sum.  That host side -- the set, the exchange, iterate's walk -- is solver_set.hpp,
+// shared with pnpsolver.hip; below the kernels stands what is the Sim3Solver's.
 //
 // Three launches in the uvo_matcher handle's stream, all scratch sized at uvo_sim3solver_set_create:
 //   k_sim3_hypotheses : computeT on three points, one lane per (solver, hypothesis).  The 4 x 4 Jacobi indexes its matrices by a
@@ -17,9 +18,9 @@
 #include <cstring>
 #include <vector>
 
-#include "devmem.hpp"
 #include "matcher_priv.hpp"
 #include "sim3solver.hpp"
+#include "solver_set.hpp"
 
 namespace uvo {
 
@@ -129,13 +130,11 @@ __global__ __launch_bounds__(256) void k_sim3_finish(Sim3Dev D) {
 using namespace uvo;
 
 namespace {
-struct Solver {
-  int n = 0, n_matches = 0, max_its = 1;
+struct Solver : SetSolver {
+  int max_its = 1;
   sim3::Params params;
   sim3::Cam K1, K2;
-  sim3::State st = {0, 0};
-  std::vector<int32_t> index1;  // mvnIndices1
-  int tap_off = 0, tap_n = 0;   // the hypotheses it consumed in the last iterate call
+  bool never() const { return n < sim3::kMinSet || n < params.min_inliers; }  // bNoMore at once, nothing drawn
 };
 
 bool params_ok(const uvo_sim3solver_params& q) {
@@ -145,75 +144,80 @@ bool params_ok(const uvo_sim3solver_params& q) {
 int max_its_of(int n, const sim3::Params& p) { return n >= sim3::kMinSet ? sim3::derive_max_its(n, p) : 1; }
 }  // namespace
 
-struct uvo_sim3solver_set {
+struct uvo_sim3solver_set : SolverSet<Sim3Call, Sim3Result> {
   uvo_matcher* m = nullptr;
-  int max_solvers = 0, max_points = 0, words = 0, total = 0;
-  DevMem mem;  // owns D's block and the page-locked mirrors of its two exchanges
   Sim3Dev D;
   float *x1c = nullptr, *x2c = nullptr, *p1 = nullptr, *p2 = nullptr, *e1 = nullptr, *e2 = nullptr;  // writable views of D's
-  Sim3Call* h_call = nullptr;  // the upload: call records, then subset records
-  int32_t* h_sub = nullptr;
-  Sim3Result* h_res = nullptr;  // the download: result records, then the returned sets
-  uint64_t* h_om = nullptr;
   std::vector<Solver> solvers;
-  std::vector<int32_t> avail;  // draw_subset's slots
-  std::vector<char> seen;      // per solver: listed in the current call
+  // the matcher's stream moves when the handle is attached to an extractor: every entry that enqueues reads it again
+  uvo_sim3solver_set* follow() { return device = m->device, stream = m->stream, this; }
+
+  // what solver_set.hpp asks of a family
+  static constexpr int kMaxSolvers = kSim3MaxSolvers, kMinPoints = sim3::kMinSet, kMaxPoints = kSim3MaxPoints, kHypPerSolver = kSim3HypPerSolver;
+  static constexpr int kSubsetStride = kSim3SubsetStride;
+  static constexpr const char* kRangeText = "Sim3Solver set: 1..64 solvers of 3..16384 points";
+  static constexpr const char* kNoMemText = "Sim3Solver set allocation failed";
+  static constexpr const char* kFullText = "the Sim3Solver set is full";
+  void arrays(Carve& c, bool scratch) {
+    const size_t S = (size_t)max_solvers, N = (size_t)max_points, W = (size_t)words, T = (size_t)total;
+    if (!scratch) c.take(x1c, S * N * 3).take(x2c, S * N * 3).take(p1, S * N * 2).take(p2, S * N * 2).take(e1, S * N).take(e2, S * N);
+    else c.take(D.hyp, T * kSim3HypFloats).take(D.counts, T).take(D.masks, T * W);
+  }
+  static int min_set(const Solver&) { return sim3::kMinSet; }
+  // the loop condition is an AND: never more than max_its <= 320 hypotheses, a solver's share of the set's slots
+  static int plan(const Solver& v, int n_iterations) { return v.never() ? 0 : sim3::iterations_ahead(v.iterations, v.max_its, n_iterations); }
+  static Sim3Call call(int id, const Solver& v, int off, int K, int) {
+    return Sim3Call{id, v.n, v.params.min_inliers, v.max_its, v.iterations, v.best_count, off, K, v.K1, v.K2};
+  }
+  void launch(int n_ids, int total) const {
+    {
+      Profiler::Scope ps(&m->prof, "k_sim3_hypotheses", stream);
+      hipLaunchKernelGGL(k_sim3_hypotheses, dim3((total + kSim3HypLanes - 1) / kSim3HypLanes), dim3(kSim3HypLanes), 0, stream, D, total);
+    }
+    {
+      Profiler::Scope ps(&m->prof, "k_sim3_score", stream);
+      hipLaunchKernelGGL(k_sim3_score, dim3(total), dim3(256), 0, stream, D);
+    }
+    {
+      Profiler::Scope ps(&m->prof, "k_sim3_finish", stream);
+      hipLaunchKernelGGL(k_sim3_finish, dim3(n_ids), dim3(256), 0, stream, D);
+    }
+  }
+  // too few points, or mnIterations has reached mRansacMaxIts
+  static int idle_no_more(const Solver& v) { return v.never() || v.iterations >= v.max_its ? 1 : 0; }
+  static bool adopt(Solver&, const Sim3Result& r, uvo_sim3solver_result* result) {
+    if (r.returned < 0) return false;
+    std::memcpy(result->T12, r.hyp, 64);
+    std::memcpy(result->R12, r.hyp + 16, 36);
+    std::memcpy(result->t12, r.hyp + 25, 12);
+    result->scale = r.hyp[28];
+    return true;
+  }
 };
 
 extern "C" {
 
-void uvo_sim3solver_set_destroy(uvo_sim3solver_set* s) {
-  if (!s) return;
-  hipSetDevice(s->m->device);
-  if (s->m->stream) hipStreamSynchronize(s->m->stream);
-  s->mem.release_all();
-  delete s;
-}
+void uvo_sim3solver_set_destroy(uvo_sim3solver_set* s) { set_destroy(s ? s->follow() : s); }
 
 int uvo_sim3solver_set_create(uvo_matcher* m, int max_solvers, int max_points, uvo_sim3solver_set** out) {
   if (!m || !out) return fail(UVO_E_BADARG, "null pointer");
   *out = nullptr;
-  if (max_solvers < 1 || max_solvers > kSim3MaxSolvers || max_points < sim3::kMinSet || max_points > kSim3MaxPoints)
-    return fail(UVO_E_BADARG, "Sim3Solver set: 1..64 solvers of 3..16384 points");
-  uvo_sim3solver_set* s = new uvo_sim3solver_set();
+  uvo_sim3solver_set* s = nullptr;
+  RC(set_create(m->device, m->stream, max_solvers, max_points, &s));
   s->m = m;
-  s->max_solvers = max_solvers, s->max_points = max_points, s->words = (max_points + 63) / 64, s->total = max_solvers * kSim3HypPerSolver;
-  const size_t S = (size_t)max_solvers, N = (size_t)max_points, W = (size_t)s->words, T = (size_t)s->total;
   Sim3Dev& D = s->D;
   D.max_points = max_points, D.words = s->words;
-  // each exchange is one copy: its two arrays are adjacent, on the device and in the mirror
-  auto upload = [&](Carve& c, auto*& call, auto*& sub) { c.take(call, S).take(sub, T * kSim3SubsetStride, alignof(int32_t)); };
-  auto download = [&](Carve& c, auto*& res, auto*& om) { c.take(res, S).take(om, S * W, alignof(uint64_t)); };
-  int rc = hipSetDevice(m->device) == hipSuccess ? UVO_OK : fail(UVO_E_NOMEM, "Sim3Solver set allocation failed");
-  if (!rc) rc = alloc_carved(s->mem, [&](Carve& c) {
-    c.take(s->x1c, S * N * 3).take(s->x2c, S * N * 3).take(s->p1, S * N * 2).take(s->p2, S * N * 2).take(s->e1, S * N).take(s->e2, S * N);
-    upload(c, D.call, D.sub);
-    c.take(D.hyp, T * kSim3HypFloats).take(D.counts, T).take(D.masks, T * W);
-    download(c, D.result, D.out_mask);
-  });
-  if (!rc) rc = alloc_carved(s->mem, [&](Carve& c) { upload(c, s->h_call, s->h_sub); }, true);
-  if (!rc) rc = alloc_carved(s->mem, [&](Carve& c) { download(c, s->h_res, s->h_om); }, true);
-  if (rc) return uvo_sim3solver_set_destroy(s), rc;
   D.x1c = s->x1c, D.x2c = s->x2c, D.p1 = s->p1, D.p2 = s->p2, D.e1 = s->e1, D.e2 = s->e2;
-  s->avail.resize(N);
-  s->seen.resize(S);
-  s->solvers.reserve(S);
+  D.call = s->d_call, D.sub = s->d_sub, D.result = s->d_res, D.out_mask = s->d_om;
   *out = s;
   return UVO_OK;
 }
 
-int uvo_sim3solver_set_clear(uvo_sim3solver_set* s) {
-  if (!s) return fail(UVO_E_BADARG, "null handle");
-  s->solvers.clear();
-  return UVO_OK;
-}
+int uvo_sim3solver_set_clear(uvo_sim3solver_set* s) { return set_clear(s); }
 
 int uvo_sim3solver_add(uvo_sim3solver_set* s, const float* x1w, const float* x2w, const float* sigma2_1, const float* sigma2_2, const int32_t* index1,
                        int n, int n_matches, const uvo_sim3_keyframe* kf1, const uvo_sim3_keyframe* kf2, const uvo_sim3solver_params* params, int* id) {
-  if (!s || !kf1 || !kf2 || !params || !id) return fail(UVO_E_BADARG, "null pointer");
-  if (n < 0 || n > s->max_points || n_matches < n) return fail(UVO_E_BADARG, "point count outside 0..max_points, or more points than matches");
-  if (n > 0 && (!x1w || !x2w || !sigma2_1 || !sigma2_2 || !index1)) return fail(UVO_E_BADARG, "null pointer");
-  if ((int)s->solvers.size() >= s->max_solvers) return fail(UVO_E_BADARG, "the Sim3Solver set is full");
+  RC(add_check(s, kf1 && kf2 && params && id, n, n_matches, x1w && x2w && sigma2_1 && sigma2_2 && index1));
   if (!params_ok(*params)) return fail(UVO_E_BADARG, "Sim3Solver parameters: probability in (0,1), min_inliers >= 0, max_iterations 1..320");
   for (const uvo_sim3_keyframe* kf : {kf1, kf2}) {
     bool ok = kf->fx == kf->fx && kf->fy == kf->fy && kf->cx == kf->cx && kf->cy == kf->cy;
@@ -231,8 +235,7 @@ int uvo_sim3solver_add(uvo_sim3solver_set* s, const float* x1w, const float* x2w
   v.params = sim3::Params{params->probability, params->min_inliers, params->max_iterations};
   v.max_its = max_its_of(n, v.params);
   v.K1 = sim3::Cam{kf1->fx, kf1->fy, kf1->cx, kf1->cy}, v.K2 = sim3::Cam{kf2->fx, kf2->fy, kf2->cx, kf2->cy};
-  v.index1.assign(index1, index1 + n);
-  const int sid = (int)s->solvers.size();
+  v.index.assign(index1, index1 + n);
   if (n > 0) {
     // the constructor's per-point work, once, on the host: mvX3Dc1/2, FromCameraToImage, the thresholds
     std::vector<float> buf((size_t)n * 12);
@@ -244,9 +247,9 @@ int uvo_sim3solver_add(uvo_sim3solver_set* s, const float* x1w, const float* x2w
       sim3::to_image(x2 + 3 * i, v.K2, p2 + 2 * i);
       e1[i] = sim3::max_error(sigma2_1[i]), e2[i] = sim3::max_error(sigma2_2[i]);
     }
-    UVO_HIP_CHECK(hipSetDevice(s->m->device));
-    hipStream_t st = s->m->stream;
-    const size_t N = (size_t)s->max_points;
+    UVO_HIP_CHECK(hipSetDevice(s->follow()->device));
+    hipStream_t st = s->stream;
+    const size_t N = (size_t)s->max_points, sid = s->solvers.size();
     UVO_HIP_CHECK(hipMemcpyAsync(s->x1c + sid * N * 3, x1, (size_t)n * 12, hipMemcpyHostToDevice, st));
     UVO_HIP_CHECK(hipMemcpyAsync(s->x2c + sid * N * 3, x2, (size_t)n * 12, hipMemcpyHostToDevice, st));
     UVO_HIP_CHECK(hipMemcpyAsync(s->p1 + sid * N * 2, p1, (size_t)n * 8, hipMemcpyHostToDevice, st));
@@ -255,155 +258,47 @@ int uvo_sim3solver_add(uvo_sim3solver_set* s, const float* x1w, const float* x2w
     UVO_HIP_CHECK(hipMemcpyAsync(s->e2 + sid * N, e2, (size_t)n * 4, hipMemcpyHostToDevice, st));
     UVO_HIP_CHECK(hipStreamSynchronize(st));  // the source is a local
   }
-  s->solvers.push_back(std::move(v));
-  *id = sid;
-  return UVO_OK;
+  return add_finish(s, v, id);
 }
 
 int uvo_sim3solver_set_ransac_parameters(uvo_sim3solver_set* s, int id, const uvo_sim3solver_params* params) {
-  if (!s || !params) return fail(UVO_E_BADARG, "null pointer");
-  if (id < 0 || id >= (int)s->solvers.size()) return fail(UVO_E_BADARG, "no such solver");
+  RC(solver_check(s, params != nullptr, id));
   if (!params_ok(*params)) return fail(UVO_E_BADARG, "Sim3Solver parameters: probability in (0,1), min_inliers >= 0, max_iterations 1..320");
   Solver& v = s->solvers[id];
   v.params = sim3::Params{params->probability, params->min_inliers, params->max_iterations};
   v.max_its = max_its_of(v.n, v.params);
-  v.st.iterations = 0;  // mnBestInliers and the best stay, as in the reference
+  v.iterations = 0;  // mnBestInliers and the best stay, as in the reference
   return UVO_OK;
 }
 
 int uvo_sim3solver_query(uvo_sim3solver_set* s, int id, uvo_sim3solver_info* info) {
-  if (!s || !info) return fail(UVO_E_BADARG, "null pointer");
-  if (id < 0 || id >= (int)s->solvers.size()) return fail(UVO_E_BADARG, "no such solver");
+  RC(solver_check(s, info != nullptr, id));
   const Solver& v = s->solvers[id];
-  *info = uvo_sim3solver_info{v.n, v.max_its, v.st.iterations, v.st.best_count};
+  *info = uvo_sim3solver_info{v.n, v.max_its, v.iterations, v.best_count};
   return UVO_OK;
 }
 
 int uvo_sim3solver_iterate(uvo_sim3solver_set* s, const int32_t* ids, int n_ids, int n_iterations, uvo_glibc_rand* rng, uvo_sim3solver_result* result) {
-  if (!s || !rng || !result || (n_ids > 0 && !ids)) return fail(UVO_E_BADARG, "null pointer");
-  if (n_ids < 0 || n_ids > s->max_solvers) return fail(UVO_E_BADARG, "more ids than the set has solvers");
-  if (n_iterations < 1) return fail(UVO_E_BADARG, "n_iterations must be at least 1");
-  uvo_sim3solver_status* status = result->status;
-  uint8_t* mask_out = result->inliers;
-  result->returned = -1, result->solver = -1, result->n_inliers = 0, result->draws = 0, result->scale = 0.f;
-  std::fill(result->T12, result->T12 + 16, 0.f);
-  std::fill(result->R12, result->R12 + 9, 0.f);
-  std::fill(result->t12, result->t12 + 3, 0.f);
-  std::vector<char>& seen = s->seen;
-  std::fill(seen.begin(), seen.end(), 0);
-  for (int j = 0; j < n_ids; ++j) {
-    if (ids[j] < 0 || ids[j] >= (int)s->solvers.size()) return fail(UVO_E_BADARG, "no such solver");
-    if (seen[ids[j]]) return fail(UVO_E_BADARG, "a solver is listed twice in one iterate call");
-    seen[ids[j]] = 1;
-    if (mask_out && result->inliers_cap < s->solvers[ids[j]].n_matches)
-      return fail(UVO_E_CAPACITY, "inliers_cap is smaller than a listed solver's n_matches");
-  }
-  for (Solver& v : s->solvers) v.tap_off = v.tap_n = 0;
-  if (status)
-    for (int j = 0; j < n_ids; ++j) status[j] = uvo_sim3solver_status{0, 0, s->solvers[ids[j]].st.iterations};
-  // every subset of the call, from a copy of the caller's state: solver k's subsets start where solver k-1's full 3 * h draws end,
-  // which is the stream position in the only case in which solver k is reached
-  pnps::GlibcRand g;
-  std::memcpy(&g, rng, sizeof g);
-  Sim3Call* call = s->h_call;
-  int32_t* sub = s->h_sub;
-  int total = 0;
-  for (int j = 0; j < n_ids; ++j) {
-    const Solver& v = s->solvers[ids[j]];
-    const bool never = v.n < sim3::kMinSet || v.n < v.params.min_inliers;  // bNoMore at once, nothing drawn
-    const int K = never ? 0 : sim3::iterations_ahead(v.st.iterations, v.max_its, n_iterations);
-    call[j] = Sim3Call{ids[j], v.n, v.params.min_inliers, v.max_its, v.st.iterations, v.st.best_count, total, K, v.K1, v.K2};
-    for (int h = 0; h < K; ++h) {
-      int32_t* rec = sub + (size_t)(total + h) * kSim3SubsetStride;
-      rec[0] = j;
-      pnps::draw_subset(g, v.n, sim3::kMinSet, s->avail.data(), rec + 1);
-    }
-    total += K;
-  }
-  const Sim3Result* res = s->h_res;
-  const size_t W = (size_t)s->words;
-  if (total > 0) {
-    uvo_matcher* m = s->m;
-    UVO_HIP_CHECK(hipSetDevice(m->device));
-    hipStream_t st = m->stream;
-    UVO_HIP_CHECK(hipMemcpyAsync(const_cast<Sim3Call*>(s->D.call), call, (size_t)s->max_solvers * sizeof(Sim3Call) + (size_t)total * kSim3SubsetStride * 4,
-                                 hipMemcpyHostToDevice, st));
-    {
-      Profiler::Scope ps(&m->prof, "k_sim3_hypotheses", st);
-      hipLaunchKernelGGL(k_sim3_hypotheses, dim3((total + kSim3HypLanes - 1) / kSim3HypLanes), dim3(kSim3HypLanes), 0, st, s->D, total);
-    }
-    {
-      Profiler::Scope ps(&m->prof, "k_sim3_score", st);
-      hipLaunchKernelGGL(k_sim3_score, dim3(total), dim3(256), 0, st, s->D);
-    }
-    {
-      Profiler::Scope ps(&m->prof, "k_sim3_finish", st);
-      hipLaunchKernelGGL(k_sim3_finish, dim3(n_ids), dim3(256), 0, st, s->D);
-    }
-    UVO_HIP_CHECK(hipGetLastError());
-    // result records of all solver slots, then the sets of the listed ones: adjacent on the device
-    UVO_HIP_CHECK(hipMemcpyAsync(s->h_res, s->D.result, (size_t)s->max_solvers * sizeof(Sim3Result) + (size_t)n_ids * W * 8, hipMemcpyDeviceToHost, st));
-    UVO_HIP_CHECK(hipStreamSynchronize(st));
-  }
-  int draws = 0;
-  for (int j = 0; j < n_ids; ++j) {
-    Solver& v = s->solvers[ids[j]];
-    if (call[j].hyp_n == 0) {  // too few points, or mnIterations has reached mRansacMaxIts: no iteration, nothing drawn
-      const bool never = v.n < sim3::kMinSet || v.n < v.params.min_inliers;
-      if (status) status[j] = uvo_sim3solver_status{1, never || v.st.iterations >= v.max_its ? 1 : 0, v.st.iterations};
-      continue;
-    }
-    const Sim3Result& r = res[j];
-    v.st.iterations += r.performed, v.st.best_count = r.best_count;
-    v.tap_off = call[j].hyp_off, v.tap_n = r.performed;
-    draws += r.performed * sim3::kMinSet;
-    if (status) status[j] = uvo_sim3solver_status{1, r.no_more, v.st.iterations};
-    if (r.returned < 0) continue;
-    result->returned = j, result->solver = ids[j], result->n_inliers = r.inliers;
-    std::memcpy(result->T12, r.hyp, 64);
-    std::memcpy(result->R12, r.hyp + 16, 36);
-    std::memcpy(result->t12, r.hyp + 25, 12);
-    result->scale = r.hyp[28];
-    if (mask_out) {
-      std::fill(mask_out, mask_out + v.n_matches, (uint8_t)0);
-      const uint64_t* words = s->h_om + (size_t)j * W;
-      for (int i = 0; i < v.n; ++i)
-        if (words[i >> 6] >> (i & 63) & 1) mask_out[v.index1[i]] = 1;
-    }
-    break;
-  }
-  result->draws = (uint32_t)draws;  // the caller's state moves to where rand() would stand after the iterations actually performed
-  pnps::GlibcRand* gr = reinterpret_cast<pnps::GlibcRand*>(rng);
-  for (int d = 0; d < draws; ++d) (void)gr->next();
-  return UVO_OK;
+  return set_iterate(s ? s->follow() : s, ids, n_ids, n_iterations, rng, result);
 }
 
 int uvo_sim3solver_find(uvo_sim3solver_set* s, int id, uvo_glibc_rand* rng, uvo_sim3solver_result* result) {
-  if (!s) return fail(UVO_E_BADARG, "null pointer");
-  if (id < 0 || id >= (int)s->solvers.size()) return fail(UVO_E_BADARG, "no such solver");
+  RC(solver_check(s, true, id));
   const int32_t ids[1] = {id};
   return uvo_sim3solver_iterate(s, ids, 1, s->solvers[id].max_its, rng, result);
 }
 
 int uvo_sim3solver_hypotheses(uvo_sim3solver_set* s, int id, int32_t* subsets, float* T12, float* T21, int32_t* counts, int cap, int* n) {
-  if (!s || !n) return fail(UVO_E_BADARG, "null pointer");
-  if (id < 0 || id >= (int)s->solvers.size()) return fail(UVO_E_BADARG, "no such solver");
-  if (cap < 0) return fail(UVO_E_BADARG, "negative capacity");
-  const Solver& v = s->solvers[id];
-  const int m = cap < v.tap_n ? cap : v.tap_n;
-  if (m > 0 && (!subsets || !T12 || !T21 || !counts)) return fail(UVO_E_BADARG, "null pointer");
-  *n = m;
-  if (m == 0) return UVO_OK;
-  const int32_t* sub = s->h_sub;  // the subsets were drawn on the host
-  for (int h = 0; h < m; ++h)
-    for (int e = 0; e < 3; ++e) subsets[h * 3 + e] = sub[(size_t)(v.tap_off + h) * kSim3SubsetStride + 1 + e];
-  std::vector<float> hyp((size_t)m * kSim3HypFloats);
+  RC(tap_subsets(s, id, subsets, T12 && T21 && counts, cap, n));
+  if (*n == 0) return UVO_OK;
+  const size_t m = (size_t)*n, off = (size_t)s->solvers[id].tap_off;
+  std::vector<float> hyp(m * kSim3HypFloats);
   UVO_HIP_CHECK(hipSetDevice(s->m->device));
-  UVO_HIP_CHECK(hipMemcpy(hyp.data(), s->D.hyp + (size_t)v.tap_off * kSim3HypFloats, hyp.size() * 4, hipMemcpyDeviceToHost));
-  UVO_HIP_CHECK(hipMemcpy(counts, s->D.counts + v.tap_off, (size_t)m * 4, hipMemcpyDeviceToHost));
-  for (int h = 0; h < m; ++h) {
-    std::memcpy(T12 + (size_t)h * 16, &hyp[(size_t)h * kSim3HypFloats], 64);
-    std::memcpy(T21 + (size_t)h * 16, &hyp[(size_t)h * kSim3HypFloats + 16], 64);
+  UVO_HIP_CHECK(hipMemcpy(hyp.data(), s->D.hyp + off * kSim3HypFloats, hyp.size() * 4, hipMemcpyDeviceToHost));
+  UVO_HIP_CHECK(hipMemcpy(counts, s->D.counts + off, m * 4, hipMemcpyDeviceToHost));
+  for (size_t h = 0; h < m; ++h) {
+    std::memcpy(T12 + h * 16, &hyp[h * kSim3HypFloats], 64);
+    std::memcpy(T21 + h * 16, &hyp[h * kSim3HypFloats + 16], 64);
   }
   return UVO_OK;
 }
