@@ -342,6 +342,20 @@ int uvo_extractor_read_plane(uvo_extractor* h, int frame, int level, int which, 
 /* FAST candidates of one level: (x, y, score) int32 triples relative to the (13,13) detection border,
  * unordered; returns count via n */
 int uvo_extractor_read_candidates(uvo_extractor* h, int frame, int level, int32_t* dst_xys, int cap, int* n);
+/* The quad-tree launch of the current lane on candidate lists of the caller's choosing, in place of what the FAST kernels leave: for
+ * every problem q = frame * nlevels + level of a batch 1 .. max_batch, n_hi[q] "high" (survivors >= fastTh) and n_lo[q] "low" (x, y, score)
+ * int32 triples, the problems' lists one behind the other in hi_xys / lo_xys, coordinates relative to the (13,13) detection border; and
+ * per frame the cell-flag bytes, the full nRows x nCols grid of level 0, then of level 1 ... (flags_per_frame bytes).  The 256- or
+ * 1024-thread form is chosen as in an extract call (UVO_TUNE_OCT_WIDE_MAX).  Out, per problem: sel_count, cand_count (the gathered
+ * list: the high entries and every low entry with score >= 7 in a cell whose flag is zero), fcount (zero flags of grid positions that
+ * are cells), and the first min(sel_count, sel_cap) selected (x, y, score) triples in the kernel's order at sel_xys[3 * q * sel_cap];
+ * per call: the threads per workgroup launched, residue[0] / [1] = cursor words / flag bytes of the batch that the launch left
+ * non-zero (it promises none).  UVO_E_BADARG, with nothing on the device touched: no geometry yet, batch out of range, a coordinate
+ * outside [3, bw - 3) x [3, bh - 3) of its level's window (bw = width - 26), a score outside 0 .. 255, more than the level's candidate
+ * capacity in both lists together, the same (x, y) twice in one problem, flags_per_frame not the handle's. */
+int uvo_extractor_octree_tap(uvo_extractor* h, int batch, const int32_t* n_hi, const int32_t* n_lo, const int32_t* hi_xys, const int32_t* lo_xys,
+                             const uint8_t* cell_flags, int flags_per_frame, int32_t* sel_count, int32_t* cand_count, int32_t* fcount, int32_t* sel_xys,
+                             int sel_cap, int32_t* threads, int32_t* residue);
 
 /*
  * Per-kernel device timing, measured with HIP events on the handle's stream around every launch made while

@@ -45,3 +45,30 @@ extern "C" int emu_geom_probe(int nfeatures, float scale_factor, int nlevels, in
   delete h;
   return rc;
 }
+
+// The per-level geometry of a width x height image on a handle sized for exactly that image: lv[16 * l + ..] = w, h, bw, bh, nCols, nRows,
+// wCell, hCell, n_cells, quota, cand_cap, nIni, sel_cap, flag base, 0, 0; is_cell[flag base + i * nCols + j] = 1 where grid position (i, j)
+// of the level is a FAST cell (the cell-flag layout of fast_levels()).  -> bytes of the flag array per frame, or < 0: the code of build_geom.
+extern "C" int emu_geom_levels(int nfeatures, float scale_factor, int nlevels, int width, int height, int* lv, unsigned char* is_cell, int is_cell_cap) {
+  using namespace uvo;
+  uvo_extractor* h = new uvo_extractor();
+  h->cfg = uvo_extractor_cfg{nfeatures, scale_factor, nlevels, 0, 20, width, height, 1, 0, 0};
+  build_ctor_tables(h);
+  Geom g;
+  std::vector<CellDesc> cells;
+  std::vector<int32_t> cell_flag;
+  int rc = build_geom(h, width, height, g, cells, &cell_flag);
+  if (rc == UVO_OK) {
+    rc = fast_flags_per_frame(g);
+    int base = 0;
+    for (int l = 0; l < nlevels; ++l) {
+      const LevelGeom& L = g.lv[l];
+      const int v[16] = {L.w, L.h, L.bw, L.bh, L.nCols, L.nRows, L.wCell, L.hCell, L.n_cells, L.quota, L.cand_cap, L.nIni, L.sel_cap, base, 0, 0};
+      memcpy(lv + 16 * l, v, sizeof(v));
+      base += L.nRows * L.nCols;
+    }
+    for (int i = 0; i < rc && i < is_cell_cap; ++i) is_cell[i] = i < (int)cell_flag.size() && cell_flag[i] >= 0 ? 1 : 0;
+  }
+  delete h;
+  return rc;
+}

@@ -42,6 +42,8 @@ def _driver(name, flags=CXX11):
 
 ARTEFACTS = {}
 ARTEFACTS.update({n: _emu(n, SHARED) for n in ("octree_emu", "pyr_tiles_emu", "strip_plan_emu", "blur_plan_emu")})
+# the same quad-tree body with the phases run by 1024 "threads", as k_octree<1024> runs them (tests/octree_cases.py)
+ARTEFACTS["octree_emu_1024"] = Artefact("tests/emu/liboctree_emu_1024.so", "tests/emu/octree_emu.cpp", CXX, SHARED + ["-DOCT_THREADS=1024"], [])
 ARTEFACTS.update({n: _emu(n, SHARED + HIP, "hipcc") for n in ("geom_emu", "grider_geom_emu")})
 ARTEFACTS.update({n: _emu(n, SHARED + NO_FMA) for n in ("pnp_emu", "pnpsolver_emu", "sim3solver_emu", "initializer_emu", "poseopt_emu",
                                                         "sim3opt_emu", "ba_emu", "navopt_emu", "navba_emu")})
@@ -54,7 +56,7 @@ ARTEFACTS["compat_initializer"] = _driver("compat_initializer", CXX11 + ["-Itest
 ARTEFACTS["compat_driver"] = _driver("compat_driver", [f for f in CXX11 if f != "-Werror"])
 
 # what __graft_entry__.build() compiles ahead of the tests, in its order
-PREBUILT = ("octree_emu", "pyr_tiles_emu", "strip_plan_emu", "geom_emu", "grider_geom_emu", "pnp_emu", "pnpsolver_emu", "sim3solver_emu",
+PREBUILT = ("octree_emu", "octree_emu_1024", "pyr_tiles_emu", "strip_plan_emu", "geom_emu", "grider_geom_emu", "pnp_emu", "pnpsolver_emu", "sim3solver_emu",
             "initializer_emu", "kfdb_emu")
 
 

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import host_build
+from octree_cases import reference_order
 from side_model import clahe as _clahe_numpy   # the numpy statement of OpenCV 3.4's 8-bit CLAHE, kept with the other models
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -334,9 +335,7 @@ def _octree_case(rng, trial, dense):
     else:
         xs, ys = rng.integers(3, W - 3, size=P), rng.integers(3, H - 3, size=P)
     pts = np.unique(np.stack([xs, ys], 1), axis=0).reshape(-1, 2)
-    j = np.minimum((pts[:, 0] - 3) // wCell, nCols - 1)
-    i = np.minimum((pts[:, 1] - 3) // hCell, nRows - 1)
-    pts = pts[np.lexsort((pts[:, 0], pts[:, 1], j, i))]   # reference candidate order: cell-major, raster inside a cell
+    pts = reference_order(pts, nCols, nRows, wCell, hCell)   # reference candidate order: cell-major, raster inside a cell
     resp = rng.integers(1, 4 if mode == 2 else 200, size=len(pts))
     return W, H, (nCols, nRows, wCell, hCell), pts, resp, N
 

@@ -9,6 +9,7 @@ extractor / matcher fails when no HIP device is usable.
 The package directory is not a valid Python identifier; import it with
     importlib.import_module("u-vip-slam_amd")
 """
+import collections
 import ctypes
 import os
 
@@ -39,7 +40,7 @@ UVO_TUNE_ZERO_COPY_OUT, UVO_TUNE_SPIN_WAIT = 17, 18
 ABI_SYMBOLS = [
     "uvo_extractor_create", "uvo_extractor_destroy", "uvo_extractor_levels", "uvo_extractor_max_keypoints", "uvo_extractor_scale_factor", "uvo_extractor_tables",
     "uvo_extract", "uvo_extract_tracked", "uvo_extract_batch", "uvo_extract_batch_device", "uvo_host_alloc", "uvo_host_free", "uvo_host_register", "uvo_host_unregister", "uvo_host_bind_near_device", "uvo_host_bind_to_cpulist_file", "uvo_shard_plan_make", "uvo_sharder_create", "uvo_sharder_destroy", "uvo_sharder_max_keypoints", "uvo_sharder_run", "uvo_sharder_submit", "uvo_sharder_wait", "uvo_extract_batch_submit", "uvo_extract_batch_wait", "uvo_extractor_synchronize", "uvo_extractor_set_pipeline", "uvo_extractor_tune", "uvo_extractor_fast_state", "uvo_extractor_level_dims",
-    "uvo_grider_fast", "uvo_clahe", "uvo_clahe_batch_device", "uvo_extractor_read_plane", "uvo_extractor_read_candidates", "uvo_extractor_profile", "uvo_extractor_profile_only", "uvo_extractor_kernel_times",
+    "uvo_grider_fast", "uvo_clahe", "uvo_clahe_batch_device", "uvo_extractor_read_plane", "uvo_extractor_read_candidates", "uvo_extractor_octree_tap", "uvo_extractor_profile", "uvo_extractor_profile_only", "uvo_extractor_kernel_times",
     "uvo_matcher_create", "uvo_matcher_destroy", "uvo_matcher_synchronize", "uvo_hamming_knn2", "uvo_hamming_knn2_batch_device",
     "uvo_hamming_matrix", "uvo_distinctive_descriptors", "uvo_search_by_projection", "uvo_match_windows", "uvo_match_groups",
     "uvo_search_by_projection_kf", "uvo_search_by_bow", "uvo_search_for_triangulation", "uvo_search_for_triangulation_batch", "uvo_search_for_triangulation_next", "uvo_triangulate_matches", "uvo_create_new_map_points", "uvo_fuse", "uvo_fuse_batch", "uvo_project_points", "uvo_search_points_in_frustum", "uvo_sim3_decompose", "uvo_sim3_relative", "uvo_project_sim3", "uvo_search_by_projection_sim3", "uvo_search_by_sim3", "uvo_haloc_hash", "uvo_klt_create", "uvo_klt_destroy", "uvo_klt_build_pyramid", "uvo_klt_build_pyramid_from_extractor", "uvo_klt_read_level", "uvo_klt_track", "uvo_undistort_points", "uvo_klt_track_undistorted", "uvo_klt_find_fundamental", "uvo_klt_track_filtered", "uvo_klt_fm_hypotheses", "uvo_klt_solve_pnp_ransac", "uvo_klt_pnp_hypotheses", "uvo_vocabulary_create", "uvo_vocabulary_destroy", "uvo_bow_transform", "uvo_matcher_wait_extractor", "uvo_extractor_wait_matcher", "uvo_matcher_attach_extractor", "uvo_matcher_profile",
@@ -235,6 +236,7 @@ def _load():
     lib.uvo_grider_fast.argtypes = [vp, vp, ci, ci, cl, ci, ci, ci, ci, ci, vp, ci, vp]
     lib.uvo_extractor_read_plane.argtypes = [vp, ci, ci, ci, vp]
     lib.uvo_extractor_read_candidates.argtypes = [vp, ci, ci, vp, ci, vp]
+    lib.uvo_extractor_octree_tap.argtypes = [vp, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, ci, vp, vp]
     lib.uvo_extractor_profile.argtypes = [vp, ci]
     lib.uvo_extractor_profile_only.argtypes = [vp, ctypes.c_char_p]
     lib.uvo_extractor_kernel_times.argtypes = [vp, ctypes.c_char_p, ci, vp, vp, ci, vp]
@@ -513,6 +515,9 @@ def _spread_rows(names, ms):
     return out
 
 
+OctreeTap = collections.namedtuple("OctreeTap", "selected sel_count cand_count fcount threads residue")
+
+
 class ORBextractor:
     """Mirror of USLAM::ORBextractor (include/ORBextractor.h:47-95).
 
@@ -730,6 +735,31 @@ class ORBextractor:
         if rc:
             raise UvoError(rc, "uvo_extractor_read_candidates")
         return buf[:min(n.value, cap)].copy()
+
+    def octree_tap(self, problems, cell_flags, sel_cap=2048):
+        """uvo_extractor_octree_tap: the quad-tree launch on caller-given lists.  problems[frame][level] = (high, low), each an (n, 3)
+        array of (x, y, score) relative to the detection border; cell_flags (frames, flags_per_frame) uint8.  -> OctreeTap with, per
+        (frame, level), selected (list of (x, y, score) in the kernel's order), sel_count, cand_count, fcount (arrays (frames, levels)),
+        and threads, residue (cursor words, flag bytes left non-zero)."""
+        nl = lib.uvo_extractor_levels(self._h)
+        batch = len(problems)
+        lists = [[np.asarray(p[k], np.int32).reshape(-1, 3) for fr in problems for p in fr] for k in (0, 1)]
+        if any(len(fr) != nl for fr in problems):
+            raise UvoError(UVO_E_BADARG, "octree_tap: one (high, low) pair per level")
+        n_hi, n_lo = (np.array([len(a) for a in lists[k]], np.int32) for k in (0, 1))
+        hi, lo = (np.ascontiguousarray(np.concatenate(lists[k] + [np.zeros((1, 3), np.int32)])) for k in (0, 1))   # (never an empty buffer)
+        cell_flags = np.ascontiguousarray(cell_flags, np.uint8).reshape(max(batch, 1), -1)
+        sel_count, cand_count, fcount = (np.zeros(max(batch, 1) * nl, np.int32) for _ in range(3))
+        sel = np.zeros((max(batch, 1) * nl, sel_cap, 3), np.int32)
+        threads, residue = ctypes.c_int32(), np.zeros(2, np.int32)
+        rc = lib.uvo_extractor_octree_tap(self._h, batch, n_hi.ctypes.data, n_lo.ctypes.data, hi.ctypes.data, lo.ctypes.data, cell_flags.ctypes.data,
+                                          cell_flags.shape[1], sel_count.ctypes.data, cand_count.ctypes.data, fcount.ctypes.data, sel.ctypes.data, sel_cap,
+                                          ctypes.byref(threads), residue.ctypes.data)
+        if rc:
+            raise UvoError(rc, "uvo_extractor_octree_tap")
+        selected = [[list(map(tuple, sel[f * nl + l, :min(int(sel_count[f * nl + l]), sel_cap)].tolist())) for l in range(nl)] for f in range(batch)]
+        return OctreeTap(selected, sel_count.reshape(batch, nl), cand_count.reshape(batch, nl), fcount.reshape(batch, nl), threads.value,
+                         tuple(int(v) for v in residue))
 
     def profile(self, enable=True, only=None):
         """Per-kernel HIP-event timing; only = a kernel name restricts it to that kernel (two event records per launch cost ~3 %)."""

@@ -699,6 +699,102 @@ int uvo_extractor_read_candidates(uvo_extractor* h, int frame, int level, int32_
   return UVO_OK;
 }
 
+// The quad-tree launch on lists of the caller's choosing.  What a list may hold is what k_fast_score can leave behind, and octree_body is
+// safe on exactly that: a coordinate inside [3, bw - 3) x [3, bh - 3) indexes the path tables (bw + bh entries), the roots (x / hX < nIni)
+// and the count pyramid (a T bin below nIni * 4^G) inside their tables and gives an order key whose in-cell parts stay below 128; at most
+// cand_cap entries in both lists together keep the gather's slots, P and the pstate words inside the level's part of the candidate block;
+// distinct coordinates make the order key unique, which is what recognises the winner of a node; and the node tables of the LDS carve
+// are sized by the quota and nIni alone (at most quota + 3 nodes, or 4 * nIni after the unconditional first pass), whatever the list.
+int uvo_extractor_octree_tap(uvo_extractor* h, int batch, const int32_t* n_hi, const int32_t* n_lo, const int32_t* hi_xys, const int32_t* lo_xys,
+                             const uint8_t* cell_flags, int flags_per_frame, int32_t* sel_count, int32_t* cand_count, int32_t* fcount, int32_t* sel_xys,
+                             int sel_cap, int32_t* threads, int32_t* residue) {
+  if (!h || !h->have_geom) return fail(UVO_E_BADARG, "no geometry yet: the tap follows a completed extract call");
+  if (batch < 1 || batch > h->cfg.max_batch) return fail(UVO_E_BADARG, "batch outside 1..max_batch");
+  if (!n_hi || !n_lo || !hi_xys || !lo_xys || !cell_flags || !sel_count || !cand_count || !fcount || !sel_xys || sel_cap < 0 || !threads || !residue)
+    return fail(UVO_E_BADARG, "null pointer");
+  const Geom& g = h->geom;
+  const int nl = g.nlevels, np = batch * nl;
+  if (flags_per_frame != fast_flags_per_frame(g)) return fail(UVO_E_BADARG, "cell flags: not the full nRows x nCols grid of every level");
+  // ---- every check, before anything on the device is touched ----
+  std::vector<uint32_t> seen;
+  size_t o_hi = 0, o_lo = 0;
+  for (int q = 0; q < np; ++q) {
+    const LevelGeom& L = g.lv[q % nl];
+    if (n_hi[q] < 0 || n_lo[q] < 0 || (int64_t)n_hi[q] + n_lo[q] > L.cand_cap) return fail(UVO_E_BADARG, "more candidates than the level's cand_cap");
+    seen.clear();
+    for (int part = 0; part < 2; ++part) {
+      const int32_t* t = part ? lo_xys + 3 * o_lo : hi_xys + 3 * o_hi;
+      for (int i = 0; i < (part ? n_lo[q] : n_hi[q]); ++i) {
+        const int x = t[3 * i], y = t[3 * i + 1], s = t[3 * i + 2];
+        if (x < 3 || x >= L.bw - 3 || y < 3 || y >= L.bh - 3) return fail(UVO_E_BADARG, "candidate outside [3, bw - 3) x [3, bh - 3) of its level");
+        if (s < 0 || s > 255) return fail(UVO_E_BADARG, "candidate score outside 0..255");
+        seen.push_back((uint32_t)x | (uint32_t)y << 16);
+      }
+    }
+    std::sort(seen.begin(), seen.end());
+    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return fail(UVO_E_BADARG, "the same (x, y) twice in one problem");
+    o_hi += (size_t)n_hi[q], o_lo += (size_t)n_lo[q];
+  }
+  UVO_HIP_CHECK(hipSetDevice(h->device));
+  int rc = prepare_octree(g);
+  if (rc) return rc;
+  Lane& LN = h->lane[h->cur];
+  const LaneScratch& d = LN.d;
+  UVO_HIP_CHECK(hipStreamSynchronize(LN.stream));
+  // ---- the lists where k_fast_score leaves them: survivors >= fastTh in front of the candidate array, the others packed in the low list ----
+  std::vector<uint32_t> a, b;
+  std::vector<int32_t> cur(2 * (size_t)np);
+  o_hi = o_lo = 0;
+  for (int q = 0; q < np; ++q) {
+    const size_t co = (size_t)(q / nl) * g.cand_block + g.lv[q % nl].cand_off;
+    a.resize((size_t)n_hi[q]), b.resize((size_t)n_hi[q]);
+    for (int i = 0; i < n_hi[q]; ++i) {
+      const int32_t* t = hi_xys + 3 * (o_hi + i);
+      a[i] = (uint32_t)t[0] | (uint32_t)t[1] << 16, b[i] = (uint32_t)t[2];
+    }
+    if (n_hi[q]) {
+      UVO_HIP_CHECK(hipMemcpy(d.cand_xy + co, a.data(), (size_t)4 * n_hi[q], hipMemcpyHostToDevice));
+      UVO_HIP_CHECK(hipMemcpy(d.cand_sc + co, b.data(), (size_t)4 * n_hi[q], hipMemcpyHostToDevice));
+    }
+    a.resize((size_t)n_lo[q]);
+    for (int i = 0; i < n_lo[q]; ++i) {
+      const int32_t* t = lo_xys + 3 * (o_lo + i);
+      a[i] = (uint32_t)t[0] | (uint32_t)t[1] << 12 | (uint32_t)t[2] << 24;
+    }
+    if (n_lo[q]) UVO_HIP_CHECK(hipMemcpy(d.cand_lo + co, a.data(), (size_t)4 * n_lo[q], hipMemcpyHostToDevice));
+    cur[2 * q] = n_hi[q], cur[2 * q + 1] = n_lo[q];
+    o_hi += (size_t)n_hi[q], o_lo += (size_t)n_lo[q];
+  }
+  UVO_HIP_CHECK(hipMemcpy(d.cursor, cur.data(), cur.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  UVO_HIP_CHECK(hipMemcpy(d.cell_hi, cell_flags, (size_t)batch * flags_per_frame, hipMemcpyHostToDevice));
+  *threads = batch * nl <= h->oct.wide_max_problems ? 1024 : 256;  // (launch_octree's choice, octree.hip)
+  rc = launch_octree(LN.stream, h->oct, h->d_lv, g, d, batch, h->d_oct_tab);
+  if (rc) return rc;
+  UVO_HIP_CHECK(hipGetLastError());
+  UVO_HIP_CHECK(hipStreamSynchronize(LN.stream));
+  // ---- what the launch left ----
+  UVO_HIP_CHECK(hipMemcpy(sel_count, d.sel_count, (size_t)4 * np, hipMemcpyDeviceToHost));
+  UVO_HIP_CHECK(hipMemcpy(cand_count, d.cand_count, (size_t)4 * np, hipMemcpyDeviceToHost));
+  UVO_HIP_CHECK(hipMemcpy(fcount, d.fcount, (size_t)4 * np, hipMemcpyDeviceToHost));
+  for (int q = 0; q < np; ++q) {
+    const LevelGeom& L = g.lv[q % nl];
+    const int m = std::min(std::min((int)sel_count[q], L.sel_cap), sel_cap);
+    if (m <= 0) continue;
+    const size_t so = (size_t)(q / nl) * g.sel_block + L.sel_off;
+    a.resize((size_t)m), b.resize((size_t)m);
+    UVO_HIP_CHECK(hipMemcpy(a.data(), d.sel_xy + so, (size_t)4 * m, hipMemcpyDeviceToHost));
+    UVO_HIP_CHECK(hipMemcpy(b.data(), d.sel_sc + so, (size_t)4 * m, hipMemcpyDeviceToHost));
+    int32_t* dst = sel_xys + (size_t)3 * q * sel_cap;
+    for (int i = 0; i < m; ++i) dst[3 * i] = (int32_t)(a[i] & 0xffff), dst[3 * i + 1] = (int32_t)(a[i] >> 16), dst[3 * i + 2] = (int32_t)b[i];
+  }
+  std::vector<uint8_t> fl((size_t)batch * flags_per_frame);
+  UVO_HIP_CHECK(hipMemcpy(cur.data(), d.cursor, cur.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (!fl.empty()) UVO_HIP_CHECK(hipMemcpy(fl.data(), d.cell_hi, fl.size(), hipMemcpyDeviceToHost));
+  residue[0] = (int32_t)std::count_if(cur.begin(), cur.end(), [](int32_t v) { return v != 0; });
+  residue[1] = (int32_t)std::count_if(fl.begin(), fl.end(), [](uint8_t v) { return v != 0; });
+  return UVO_OK;
+}
+
 int uvo_extractor_profile(uvo_extractor* h, int enable) {
   if (!h) return fail(UVO_E_BADARG, "null handle");
   UVO_HIP_CHECK(hipSetDevice(h->device));
